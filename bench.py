@@ -1,8 +1,15 @@
 """Benchmark: temporal edges/s of the fused TGN(N) train step on tgbl-wiki-shaped batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps of the headline model and prints the result line.  --full adds
+everything else the benchmark measures (per-launch probes and roofline, the validation pass, the secondary model
+path, the config-#1 line, the drop-in train loop, the t-CSR sampler, the CPU baselines); the --no-* switches and
+--only then leave single legs out.  --dump-outputs DIR: after the timed steps the timed path runs a few steps again
+from the run's initial state and the outputs of the last of them are written as DIR/<name>.npy, reproducible to
+rounding from run to run (see dump_replay).
 
 A step is one train batch.  Headline (--model tgn, the north star): the TGN memory path
 (modules/memory_module.py + msg_func/msg_agg + emb_module TransformerConv + decoder LinkPredictor,
@@ -113,6 +120,75 @@ def _metric(dataset: str, model: str) -> str:
             f"temporal edges/sec on {dataset} TGNN, running DGL block-loop path (train step)")
 
 
+DUMP_ARRAY_BYTES = 8 << 20   # per dumped array (at most 6 arrays: well inside 64 MB in all)
+DUMP_STEPS = 4               # steps of the --dump-outputs replay (see dump_replay)
+
+
+def dump_snapshot(tensors):
+    """The run's initial state (parameters, memory table, last-update times), taken before the first step."""
+    return [(t, t.detach().clone()) for t in tensors]
+
+
+def dump_replay(eng, snap, n, use_graph):
+    """--dump-outputs: the timed path (the same engine, bound split and captured graphs) run again after the timed
+    window for n = min(--steps, DUMP_STEPS) steps from the run's initial state: parameters, memory and last-update
+    times as before the first step, Adam moments and step count zero, rings and message stores reset, batch 0 first.
+    The outputs of its last step are what is written.
+
+    Why not the last timed step itself: the inputs (stream, initial parameters, negatives, dropout masks) are functions
+    of the arguments and fixed seeds, identical in every run, but the step sums with float atomics, whose order
+    varies, and the training recurrence (memory, Adam) amplifies that rounding.  On one MI355X two runs were
+    bit-identical after 1 step, within 3e-7 after 5 and 2e-6 after 20 (parameters, memory, scores), and apart by
+    1e-2 .. 1e-1 in the scores after 80; after a 300-step window by up to 0.9.  The short replay stays at rounding,
+    so two runs, or two builds, can be compared output for output."""
+    eng.finish()
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for t, t0 in snap:
+            t.copy_(t0)
+        eng.adam_m.zero_()
+        eng.adam_v.zero_()
+    eng.ctl[4] = 0                                     # TGNX_CTL_ADAM_T
+    eng.ctl[12:13].view(torch.float64).zero_()         # TGNX_CTL_LOSS
+    eng.begin_epoch()
+    if use_graph:
+        eng.replay_resident_n(n)
+    else:
+        for _ in range(n):
+            eng.resident_train_step()
+    eng.finish()
+    torch.cuda.synchronize()
+    eng.check()
+    return eng.loss_sum()
+
+
+def last_batch_rows(start, steps, nb_epoch, split_events, Bg, world):
+    """Rows of out_pos / out_neg the last timed step (batch start + steps - 1 of the epoch sequence) wrote on one
+    rank: its share of that batch's events (the epoch's last batch is the short one)."""
+    i = (start + steps - 1) % nb_epoch
+    n = min(Bg, split_events - i * Bg)
+    return -(-n // world)
+
+
+def dump_outputs(path, arrays):
+    """Write arrays as path/<name>.npy (float32; float64 for integer / double arrays).  An array above
+    DUMP_ARRAY_BYTES is written as a fixed sample of its rows (seed 0, ascending row order: the same rows in every
+    run); the choice depends on the array's shape alone."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.reshape(-1, 1) if t.dim() < 2 else t.reshape(t.shape[0], -1)
+        wide = t.dtype in (torch.float64, torch.int64)
+        row_bytes = t.shape[1] * (8 if wide else 4)
+        keep = max(1, DUMP_ARRAY_BYTES // row_bytes)
+        if t.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy().astype(np.float64 if wide else np.float32)
+        np.save(os.path.join(path, name + ".npy"), a[:, 0] if a.shape[1] == 1 else a)
+    _log(f"dump-outputs: {', '.join(arrays)} -> {path}")
+
+
 def timed_window(nb_epoch, steps, warmup, mode):
     """The timed window: `steps` consecutive batches from batch `start` of the train epoch (0-based).  mid: centred
     in the epoch (rings and message stores in their steady state; an early window samples partly empty rings),
@@ -196,6 +272,7 @@ def run_tgnn(args, world, rank, dev, probe=True):
     loader = LastNeighborLoader(N, K, device=dev)
     dst_nodes = torch.from_numpy(np.unique(stream.dst))
     eng = TgnnEngine(model, loader, ev["msg"], opt, dst_nodes=dst_nodes, seed=1234, rank=rank, world=world)
+    snap = dump_snapshot([model.flat, model.memory.memory, model.memory.last_update_t]) if args.dump_outputs else None
     neg_buf = torch.zeros(stream.num_events, dtype=torch.long, device=dev)
     eng.bind_resident(ev["src"], ev["dst"], ev["t"], ev["blk"], ev["msg"], neg_buf, 0, stream.train_end, Bg,
                       dropout=not args.no_dropout)
@@ -245,6 +322,16 @@ def run_tgnn(args, world, rank, dev, probe=True):
     eng.check()
     loss = eng.loss_sum()
     assert math.isfinite(loss), "non-finite loss"
+    if args.dump_outputs:   # (every rank replays: the steps hold collectives; rank 0 writes)
+        n = min(args.steps, DUMP_STEPS)
+        dloss = dump_replay(eng, snap, n, use_graph)
+        counter["i"] = n
+        if rank == 0:
+            rows = last_batch_rows(0, n, nb_epoch, stream.train_end, Bg, world)
+            dump_outputs(args.dump_outputs, {"pos": eng.out_pos[:rows], "neg": eng.out_neg[:rows],
+                                             "loss_sum": torch.tensor([dloss], dtype=torch.float64),
+                                             "memory": model.memory.memory,
+                                             "last_update": model.memory.last_update_t, "params": model.flat})
 
     # live kernel timing (HIP events on the launch stream) for the roofline, over the TIMED window: before each
     # kernel's probe the epoch is rewound (begin_epoch) and replayed to batch `start`, then the probe's eager steps
@@ -285,7 +372,8 @@ def run_tgnn(args, world, rank, dev, probe=True):
     blocks_mean = float(np.mean([blk[i:i + Bg].max() + 1 for i in range(0, stream.train_end, Bg)]))
     if not probes:
         return {"metric": _metric(args.dataset, "tgnn"), "value": round(args.steps * Bg / elapsed, 1),
-                "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+                "unit": "events/s", "n_gpus": _group_size(world), "higher_is_better": True, "dtype": "f32",
+                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "warmup": args.warmup,
                 "steps": args.steps, "timed_window": window_note, "loss_sum": round(loss, 4),
                 "config": {"timed_steps": [prefill + args.warmup, prefill + args.warmup + args.steps]},
                 "edges_per_step": round((e1 - e0) / args.steps / world, 1),
@@ -478,6 +566,7 @@ def run_tgn(args, world, rank, dev):
     loader = LastNeighborLoader(N, K, device=dev)
     eng = TgnEngine(model, loader, dict(src=stream.src, dst=stream.dst, t=stream.t.astype(np.float32), msg=stream.msg),
                     opt, dst_nodes=np.unique(stream.dst), seed=1234, rank=rank, world=world)
+    snap = dump_snapshot([model.flat, model.memory.memory, model.memory.last_update]) if args.dump_outputs else None
     eng.keep_grads = False    # nothing reads the gradient buffer (world 1: TGNX_TGN_NO_GRAD_STORE)
     eng.bind_resident(0, stream.train_end, Bg, dropout=not args.no_dropout)
     nb_epoch = math.ceil(stream.train_end / Bg)
@@ -539,7 +628,18 @@ def run_tgn(args, world, rank, dev):
     eng.check()
     loss = eng.loss_sum()
     assert math.isfinite(loss), "non-finite loss"
-    _log(f"tgn: {args.steps} steps {elapsed * 1e3 / args.steps:.4f} ms/step; probes")
+    if args.dump_outputs:   # (every rank replays: the steps hold collectives; rank 0 writes)
+        n = min(args.steps, DUMP_STEPS)
+        dloss = dump_replay(eng, snap, n, use_graph)
+        counter["i"] = n
+        if rank == 0:
+            rows = last_batch_rows(0, n, nb_epoch, stream.train_end, Bg, world)
+            dump_outputs(args.dump_outputs, {"pos": eng.out_pos[:rows], "neg": eng.out_neg[:rows],
+                                             "loss_sum": torch.tensor([dloss], dtype=torch.float64),
+                                             "memory": model.memory.memory, "last_update": model.memory.last_update,
+                                             "params": model.flat})
+    _log(f"tgn: {args.steps} steps {elapsed * 1e3 / args.steps:.4f} ms/step"
+         + ("" if args.no_probe else "; probes"))
     ms_step = elapsed / args.steps * 1e3
     value = args.steps * Bg / elapsed
 
@@ -591,7 +691,9 @@ def run_tgn(args, world, rank, dev):
                            "parallelism": f"dp{world}", "layers": args.layers, "timed_window": window_note,
                            "timed_steps": [prefill + args.warmup, prefill + args.warmup + args.steps],
                            "sampled_edges_per_step": round(win_edges, 1)},
-                "roofline": None, "note": "--no-probe: no per-launch probes", "loss_sum": round(loss, 4)}
+                "roofline": None, "loss_sum": round(loss, 4),
+                "note": "--no-probe: no per-launch probes" if args.full else
+                        "plain run: the timed window only (--full adds the probes and the other legs)"}
     kvf = args.layers == 1 and "tgn_kv_dE" not in probes
     for name, q in probes.items():
         algo = tgn_launch_bytes(name, q["edges"], q["nodes"], Bw, Bg, D, d, K, P, N, kvf) * (
@@ -735,7 +837,7 @@ def tgnn_config1_gpu(args, dev):
     import copy
     a = copy.copy(args)
     a.batch, a.steps, a.warmup = 2000, min(args.steps, 40), min(args.warmup, 5)
-    a.dataset = "tgbl-wiki"
+    a.dataset, a.dump_outputs = "tgbl-wiki", None
     r = run_tgnn(a, 1, 0, dev, probe=False)
     r.update(unit="events/s", batch=2000, dtype="f32",
              workload="tgbl-wiki TGNN (running reference path: DGL EdgeGATConv block loop), config/TGN.yml "
@@ -885,6 +987,13 @@ def main():
                     help="TGN attention hops (2: the comment config's 2-hop temporal attention)")
     ap.add_argument("--updater", choices=["gru", "rnn"], default="gru",
                     help="TGN memory updater (rnn: DyRepMemory memory_updater_type 'rnn')")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-launch probes + roofline, validation "
+                         "pass, secondary path, config-#1 line, train loop, t-CSR sampler, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, replay min(steps, 4) steps of the timed path from the initial state "
+                         "and write the last one's outputs (pos / neg scores, loss sum, memory, last_update, "
+                         "parameters) as DIR/<name>.npy")
     ap.add_argument("--only", action="store_true", help="skip the secondary path")
     ap.add_argument("--no-dropout", action="store_true", help="train mode without dropout")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -901,6 +1010,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="rehearsal only: 'gloo' to run N>1 on one device")
     ap.add_argument("--one-device", action="store_true", help="rehearsal only: every rank on cuda:0")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline model's timed window and nothing else
+        args.only = args.no_probe = args.no_cpu_baseline = args.no_train_loop = args.no_tcsr = args.no_config1 = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_spawn_ranks(args))
@@ -921,6 +1032,7 @@ def main():
     out = run[args.model](args, world, rank, dev)
     if not args.only:
         other = "tgnn" if args.model == "tgn" else "tgn"
+        args.dump_outputs = None   # (the headline path's outputs only)
         sec = run[other](args, world, rank, dev)
         out["secondary_path"] = {"model": other, "workload": sec.get("config", {}).get("workload"),
                                  "value": sec["value"], "unit": sec.get("unit", "events/s"),
