@@ -548,6 +548,72 @@ int tgnx_edge_attn_bwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t ch
                        const float* q, const float* k, const float* v, const float* e, const int64_t* indptr,
                        const float* alpha, float* dq, float* dk, float* dv, float* de, void* stream);
 
+/* ---------------------------------------------------------------- per-operator backward (csrc/tgnx_ops_bwd.hip)
+ * What torch autograd needs to train a composition of the operators above (tgnx/ops.py, tgnx/nn.py).  Same
+ * conventions: row-major fp32, int64 indices, caller-provided workspace, no allocation.  Every one of them is
+ * run-to-run deterministic: no float atomics, column and row sums in an order fixed by the shapes.  Contractions
+ * run on tgnx_gemm_f32. */
+
+/* out[c] = Σ_m x[m*ldx + c] for c < N (the bias gradients), ldx >= N.  Order: rows in chunks of 256, within a
+ * chunk four strided sequential partial sums added in order, then the chunks in order.  M = 0 gives zeros.
+ * ws: tgnx_col_sum_ws_bytes(M, N) bytes. */
+size_t tgnx_col_sum_ws_bytes(int64_t M, int64_t N);
+int tgnx_col_sum(int64_t M, int64_t N, const float* x, int64_t ldx, float* out, void* ws, size_t ws_bytes,
+                 void* stream);
+
+/* Backward of tgnx_memory_cell given dh_out [M,D]: the pre-activations are recomputed (two GEMMs), one elementwise
+ * kernel forms the gate gradients (GRU in torch's r,z,n order; RNN: dh_out (1 − h'²)), then dx [M,d_in] = dgi W_ih,
+ * dh [M,D] = dh_out z + dgh W_hh, dw_ih = dgi^T x, dw_hh = dgh^T h (shapes of w_ih / w_hh) and the bias gradients
+ * [3D] (GRU) / [D] (RNN) by column sums.  Any output pointer may be NULL to skip it; b_ih / b_hh may be NULL as in
+ * the forward.  ws: tgnx_memory_cell_bwd_ws_bytes bytes. */
+size_t tgnx_memory_cell_bwd_ws_bytes(int64_t M, int64_t d_in, int64_t D);
+int tgnx_memory_cell_bwd(int32_t cell, int64_t M, int64_t d_in, int64_t D, const float* dh_out, const float* x,
+                         const float* h, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                         float* dx, float* dh, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, void* ws,
+                         size_t ws_bytes, void* stream);
+
+/* Backward of tgnx_link_predictor given dout [M] (the gradient of the sigmoid output when sigmoid = 1, of the
+ * logits otherwise).  With g_i = dout_i (σ(1 − σ) of the recomputed output) and da[i] = g_i w_out [pre-activation
+ * > 0]: dz_dst [M,d_in] = da W_dst; dz_src [n_src,d_in] = dhs W_src with dhs[j] = Σ_{i ≡ j (mod n_src)} da[i] in
+ * increasing i (the `tile` pairing); dw_src / dw_dst [D,d_in], db_src / db_dst [D], dw_out [D], db_out [1].  Any
+ * output pointer may be NULL.  ws: tgnx_link_predictor_bwd_ws_bytes bytes. */
+size_t tgnx_link_predictor_bwd_ws_bytes(int64_t n_src, int64_t M, int64_t d_in, int64_t D);
+int tgnx_link_predictor_bwd(int64_t n_src, int64_t M, int64_t d_in, int64_t D, const float* dout, const float* z_src,
+                            const float* z_dst, const float* w_src, const float* b_src, const float* w_dst,
+                            const float* b_dst, const float* w_out, const float* b_out, int32_t sigmoid,
+                            float* dz_src, float* dz_dst, float* dw_src, float* db_src, float* dw_dst, float* db_dst,
+                            float* dw_out, float* db_out, void* ws, size_t ws_bytes, void* stream);
+
+/* TimeEncoder ([ext] torch_geometric TimeEncoder; modules/time_enc.py is absent from the reference):
+ * out[n,D] = cos(fmaf(w[c], t[i], b[c])) with the exact argument reduction of the fused steps (csrc/tgnx_math.h).
+ * Backward: dw[c] = Σ_i −sin(·) t[i] dout[i,c], db[c] = Σ_i −sin(·) dout[i,c], fused as one column reduction (no
+ * [n,D] temporary); dw / db may be NULL.  t is data: no gradient.  ws: tgnx_time_encode_bwd_ws_bytes bytes. */
+int tgnx_time_encode(int64_t n, int64_t D, const float* t, const float* w, const float* b, float* out, void* stream);
+size_t tgnx_time_encode_bwd_ws_bytes(int64_t n, int64_t D);
+int tgnx_time_encode_bwd(int64_t n, int64_t D, const float* t, const float* w, const float* b, const float* dout,
+                         float* dw, float* db, void* ws, size_t ws_bytes, void* stream);
+
+/* TimeEmbedding (JODIE's projection, modules/emb_module.py:32-52): out[n,D] = x (1 + w[c] rel_t[i] + b[c]).
+ * Backward: dx = dout (1 + w rel_t + b), dw[c] = Σ_i dout x rel_t, db[c] = Σ_i dout x; dx / dw / db may be NULL.
+ * ws: tgnx_time_embedding_bwd_ws_bytes bytes. */
+int tgnx_time_embedding(int64_t n, int64_t D, const float* x, const float* rel_t, const float* w, const float* b,
+                        float* out, void* stream);
+size_t tgnx_time_embedding_bwd_ws_bytes(int64_t n, int64_t D);
+int tgnx_time_embedding_bwd(int64_t n, int64_t D, const float* x, const float* rel_t, const float* w, const float* b,
+                            const float* dout, float* dx, float* dw, float* db, void* ws, size_t ws_bytes,
+                            void* stream);
+
+/* Backward of tgnx_msg_agg.  last: dmsg [n_msg,dim] is zeroed, then dmsg[argmax[r]] = dout[r] for the rows with
+ * argmax[r] < n_msg (argmax as the forward wrote it): a scatter, exact.  mean: dmsg[p] = dout[index[p]] /
+ * count[index[p]], the counts from an integer histogram; an index outside [0, dim_size) gets a zero row and is
+ * counted into *n_invalid (a device int64 the caller zeroes; may be NULL).  ws (mean):
+ * tgnx_msg_agg_mean_bwd_ws_bytes(dim_size) bytes. */
+int tgnx_msg_agg_last_bwd(const float* dout, const int64_t* argmax, int64_t dim_size, int64_t dim, int64_t n_msg,
+                          float* dmsg, void* stream);
+size_t tgnx_msg_agg_mean_bwd_ws_bytes(int64_t dim_size);
+int tgnx_msg_agg_mean_bwd(const float* dout, const int64_t* index, int64_t n_msg, int64_t dim, int64_t dim_size,
+                          float* dmsg, int64_t* n_invalid, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,10 @@
 //   gru_update                               TGNMemory.memory_updater GRUCell / RNNCell (memory_module.py:70-78)
 //   predictor                                LinkPredictor (decoder.py:12-27) / EdgePredictor (model_utils.py:165-195)
 //   edge_attn_fwd / edge_attn_bwd            TransformerConv's attention (emb_module.py:21-29, PyG semantics)
+//   time_encode / time_embedding             TimeEncoder ([ext] PyG) / TimeEmbedding (emb_module.py:32-52)
+//   col_sum, gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd,
+//   msg_agg_mean_bwd                         the backward halves (csrc/tgnx_ops_bwd.hip) behind tgnx/ops.py's
+//                                            autograd functions
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -375,6 +379,215 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_attn_bwd(
   return {dq, dk, dv, de};
 }
 
+// ------------------------------------------------------------------ backward ops (csrc/tgnx_ops_bwd.hip)
+// A gradient the caller does not need (need[i] == 0) is not computed and comes back as an empty tensor.
+at::Tensor ws_bytes(const at::Tensor& ref, size_t nb) {
+  return at::empty({(int64_t)std::max<size_t>(nb, 1)}, ref.options().dtype(at::kByte));
+}
+at::Tensor grad_like(bool need, at::IntArrayRef shape, const at::Tensor& ref) {
+  return need ? at::empty(shape, ref.options()) : at::empty({0}, ref.options());
+}
+float* grad_ptr(bool need, at::Tensor& g) { return need ? g.data_ptr<float>() : nullptr; }
+
+// x [M, N] with unit column stride; rows may be strided (a column slice of a wider matrix)
+at::Tensor col_sum(const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "x must be a HIP device tensor");
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "x has dtype ", x.scalar_type(), ", expected ", at::kFloat);
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D");
+  const int64_t M = x.size(0), N = x.size(1);
+  const int64_t ldx = M > 1 ? x.stride(0) : N;
+  TORCH_CHECK(N <= 1 || x.stride(1) == 1, "x must have unit column stride");
+  TORCH_CHECK(ldx >= N, "x's rows must not overlap (row stride ", ldx, " < ", N, " columns)");
+  const c10::OptionalDeviceGuard guard(x.device());
+  at::Tensor out = at::empty({N}, x.options());
+  const size_t nb = tgnx_col_sum_ws_bytes(M, N);
+  at::Tensor ws = ws_bytes(x, nb);
+  check_rc(tgnx_col_sum(M, N, x.data_ptr<float>(), ldx, out.data_ptr<float>(), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_col_sum");
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> gru_update_bwd(
+    const at::Tensor& dh_out, const at::Tensor& x, const at::Tensor& h, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const c10::optional<at::Tensor>& b_ih, const c10::optional<at::Tensor>& b_hh,
+    int64_t cell, at::IntArrayRef need) {
+  dev_tensor(dh_out, at::kFloat, "dh_out");
+  dev_tensor(x, at::kFloat, "x");
+  dev_tensor(h, at::kFloat, "h");
+  dev_tensor(w_ih, at::kFloat, "w_ih");
+  dev_tensor(w_hh, at::kFloat, "w_hh");
+  TORCH_CHECK(cell == 0 || cell == 1, "cell 0 (GRUCell) or 1 (RNNCell, tanh)");
+  TORCH_CHECK(need.size() == 6, "need must have 6 entries (dx, dh, dw_ih, dw_hh, db_ih, db_hh)");
+  TORCH_CHECK(x.dim() == 2 && h.dim() == 2 && x.size(0) == h.size(0), "x [M, d_in] and h [M, D]");
+  TORCH_CHECK(dh_out.sizes() == h.sizes(), "dh_out must be [M, D]");
+  const int64_t M = x.size(0), d_in = x.size(1), D = h.size(1), G = (cell == 0 ? 3 : 1) * D;
+  TORCH_CHECK(w_ih.dim() == 2 && w_ih.size(0) == G && w_ih.size(1) == d_in, "w_ih must be [", G, ", ", d_in, "]");
+  TORCH_CHECK(w_hh.dim() == 2 && w_hh.size(0) == G && w_hh.size(1) == D, "w_hh must be [", G, ", ", D, "]");
+  same_device(x, {&dh_out, &h, &w_ih, &w_hh});
+  const float* bi = opt_ptr(b_ih, x, G, "b_ih");
+  const float* bh = opt_ptr(b_hh, x, G, "b_hh");
+  const c10::OptionalDeviceGuard guard(x.device());
+  at::Tensor dx = grad_like(need[0], x.sizes(), x), dh = grad_like(need[1], h.sizes(), x);
+  at::Tensor dwi = grad_like(need[2], w_ih.sizes(), x), dwh = grad_like(need[3], w_hh.sizes(), x);
+  at::Tensor dbi = grad_like(need[4], {G}, x), dbh = grad_like(need[5], {G}, x);
+  const size_t nb = tgnx_memory_cell_bwd_ws_bytes(M, d_in, D);
+  at::Tensor ws = ws_bytes(x, nb);
+  check_rc(tgnx_memory_cell_bwd((int32_t)cell, M, d_in, D, dh_out.data_ptr<float>(), x.data_ptr<float>(),
+                                h.data_ptr<float>(), w_ih.data_ptr<float>(), w_hh.data_ptr<float>(), bi, bh,
+                                grad_ptr(need[0], dx), grad_ptr(need[1], dh), grad_ptr(need[2], dwi),
+                                grad_ptr(need[3], dwh), grad_ptr(need[4], dbi), grad_ptr(need[5], dbh), ws.data_ptr(),
+                                nb, cur_stream()),
+           "tgnx_memory_cell_bwd");
+  return {dx, dh, dwi, dwh, dbi, dbh};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+predictor_bwd(const at::Tensor& dout, const at::Tensor& z_src, const at::Tensor& z_dst, const at::Tensor& w_src,
+              const c10::optional<at::Tensor>& b_src, const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst,
+              const at::Tensor& w_out, const at::Tensor& b_out, bool sigmoid, at::IntArrayRef need) {
+  dev_tensor(dout, at::kFloat, "dout");
+  dev_tensor(z_src, at::kFloat, "z_src");
+  dev_tensor(z_dst, at::kFloat, "z_dst");
+  dev_tensor(w_src, at::kFloat, "w_src");
+  dev_tensor(w_dst, at::kFloat, "w_dst");
+  dev_tensor(w_out, at::kFloat, "w_out");
+  dev_tensor(b_out, at::kFloat, "b_out");
+  TORCH_CHECK(need.size() == 8,
+              "need must have 8 entries (dz_src, dz_dst, dw_src, db_src, dw_dst, db_dst, dw_out, db_out)");
+  TORCH_CHECK(z_src.dim() == 2 && z_dst.dim() == 2 && z_src.size(1) == z_dst.size(1), "z_src [B, d] and z_dst [M, d]");
+  TORCH_CHECK(w_src.dim() == 2 && w_dst.dim() == 2, "w_src / w_dst must be [D, d]");
+  const int64_t B = z_src.size(0), M = z_dst.size(0), d_in = z_src.size(1), D = w_src.size(0);
+  TORCH_CHECK(M == 0 || (B > 0 && M % B == 0), "z_dst rows must be a multiple of z_src rows (tile pairing)");
+  TORCH_CHECK(w_src.size(1) == d_in && w_dst.size(0) == D && w_dst.size(1) == d_in, "w_src / w_dst must be [D, d]");
+  TORCH_CHECK(w_out.numel() == D && b_out.numel() == 1, "w_out must have D entries and b_out one");
+  TORCH_CHECK(dout.numel() == M, "dout must have one entry per z_dst row");
+  same_device(z_src, {&dout, &z_dst, &w_src, &w_dst, &w_out, &b_out});
+  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
+  const c10::OptionalDeviceGuard guard(z_src.device());
+  at::Tensor dzs = grad_like(need[0], z_src.sizes(), z_src), dzd = grad_like(need[1], z_dst.sizes(), z_src);
+  at::Tensor dws = grad_like(need[2], w_src.sizes(), z_src), dbs = grad_like(need[3], {D}, z_src);
+  at::Tensor dwd = grad_like(need[4], w_dst.sizes(), z_src), dbd = grad_like(need[5], {D}, z_src);
+  at::Tensor dwo = grad_like(need[6], w_out.sizes(), z_src), dbo = grad_like(need[7], b_out.sizes(), z_src);
+  const size_t nb = tgnx_link_predictor_bwd_ws_bytes(B, M, d_in, D);
+  at::Tensor ws = ws_bytes(z_src, nb);
+  check_rc(tgnx_link_predictor_bwd(B, M, d_in, D, dout.data_ptr<float>(), z_src.data_ptr<float>(),
+                                   z_dst.data_ptr<float>(), w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd,
+                                   w_out.data_ptr<float>(), b_out.data_ptr<float>(), sigmoid ? 1 : 0,
+                                   grad_ptr(need[0], dzs), grad_ptr(need[1], dzd), grad_ptr(need[2], dws),
+                                   grad_ptr(need[3], dbs), grad_ptr(need[4], dwd), grad_ptr(need[5], dbd),
+                                   grad_ptr(need[6], dwo), grad_ptr(need[7], dbo), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_link_predictor_bwd");
+  return {dzs, dzd, dws, dbs, dwd, dbd, dwo, dbo};
+}
+
+// t [n]; w ([D] or Linear(1, D)'s [D, 1]) and b [D]
+int64_t time_args(const at::Tensor& t, const at::Tensor& w, const at::Tensor& b) {
+  dev_tensor(t, at::kFloat, "t");
+  dev_tensor(w, at::kFloat, "w");
+  dev_tensor(b, at::kFloat, "b");
+  TORCH_CHECK(t.dim() == 1, "t must be [n]");
+  TORCH_CHECK(b.dim() == 1 && w.numel() == b.numel(), "w and b must have D entries each");
+  same_device(t, {&w, &b});
+  return b.numel();
+}
+
+at::Tensor time_encode(const at::Tensor& t, const at::Tensor& w, const at::Tensor& b) {
+  const int64_t D = time_args(t, w, b), n = t.numel();
+  const c10::OptionalDeviceGuard guard(t.device());
+  at::Tensor out = at::empty({n, D}, t.options());
+  check_rc(tgnx_time_encode(n, D, t.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(),
+                            out.data_ptr<float>(), cur_stream()),
+           "tgnx_time_encode");
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> time_encode_bwd(const at::Tensor& dout, const at::Tensor& t, const at::Tensor& w,
+                                                   const at::Tensor& b) {
+  const int64_t D = time_args(t, w, b), n = t.numel();
+  dev_tensor(dout, at::kFloat, "dout");
+  TORCH_CHECK(dout.dim() == 2 && dout.size(0) == n && dout.size(1) == D, "dout must be [n, D]");
+  same_device(t, {&dout});
+  const c10::OptionalDeviceGuard guard(t.device());
+  at::Tensor dw = at::empty_like(w), db = at::empty_like(b);
+  const size_t nb = tgnx_time_encode_bwd_ws_bytes(n, D);
+  at::Tensor ws = ws_bytes(t, nb);
+  check_rc(tgnx_time_encode_bwd(n, D, t.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(),
+                                dout.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(), ws.data_ptr(), nb,
+                                cur_stream()),
+           "tgnx_time_encode_bwd");
+  return {dw, db};
+}
+
+at::Tensor time_embedding(const at::Tensor& x, const at::Tensor& rel_t, const at::Tensor& w, const at::Tensor& b) {
+  const int64_t D = time_args(rel_t, w, b), n = rel_t.numel();
+  dev_tensor(x, at::kFloat, "x");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == n && x.size(1) == D, "x must be [n, D]");
+  same_device(rel_t, {&x});
+  const c10::OptionalDeviceGuard guard(x.device());
+  at::Tensor out = at::empty_like(x);
+  check_rc(tgnx_time_embedding(n, D, x.data_ptr<float>(), rel_t.data_ptr<float>(), w.data_ptr<float>(),
+                               b.data_ptr<float>(), out.data_ptr<float>(), cur_stream()),
+           "tgnx_time_embedding");
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> time_embedding_bwd(const at::Tensor& dout, const at::Tensor& x,
+                                                                  const at::Tensor& rel_t, const at::Tensor& w,
+                                                                  const at::Tensor& b, bool need_dx) {
+  const int64_t D = time_args(rel_t, w, b), n = rel_t.numel();
+  dev_tensor(x, at::kFloat, "x");
+  dev_tensor(dout, at::kFloat, "dout");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == n && x.size(1) == D, "x must be [n, D]");
+  TORCH_CHECK(dout.sizes() == x.sizes(), "dout must be [n, D]");
+  same_device(rel_t, {&x, &dout});
+  const c10::OptionalDeviceGuard guard(x.device());
+  at::Tensor dx = grad_like(need_dx, x.sizes(), x), dw = at::empty_like(w), db = at::empty_like(b);
+  const size_t nb = tgnx_time_embedding_bwd_ws_bytes(n, D);
+  at::Tensor ws = ws_bytes(x, nb);
+  check_rc(tgnx_time_embedding_bwd(n, D, x.data_ptr<float>(), rel_t.data_ptr<float>(), w.data_ptr<float>(),
+                                   b.data_ptr<float>(), dout.data_ptr<float>(), grad_ptr(need_dx, dx),
+                                   dw.data_ptr<float>(), db.data_ptr<float>(), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_time_embedding_bwd");
+  return {dx, dw, db};
+}
+
+at::Tensor msg_agg_last_bwd(const at::Tensor& dout, const at::Tensor& argmax, int64_t n_msg) {
+  dev_tensor(dout, at::kFloat, "dout");
+  dev_tensor(argmax, at::kLong, "argmax");
+  TORCH_CHECK(dout.dim() == 2, "dout must be [dim_size, dim]");
+  TORCH_CHECK(argmax.dim() == 1 && argmax.numel() == dout.size(0), "argmax must be [dim_size]");
+  TORCH_CHECK(n_msg >= 0, "n_msg must be non-negative");
+  same_device(dout, {&argmax});
+  const c10::OptionalDeviceGuard guard(dout.device());
+  at::Tensor dmsg = at::empty({n_msg, dout.size(1)}, dout.options());
+  check_rc(tgnx_msg_agg_last_bwd(dout.data_ptr<float>(), argmax.data_ptr<int64_t>(), dout.size(0), dout.size(1), n_msg,
+                                 dmsg.data_ptr<float>(), cur_stream()),
+           "tgnx_msg_agg_last_bwd");
+  return dmsg;
+}
+
+// out-of-range index -> RuntimeError, as the forward (one device -> host read of the drop count)
+at::Tensor msg_agg_mean_bwd(const at::Tensor& dout, const at::Tensor& index) {
+  dev_tensor(dout, at::kFloat, "dout");
+  dev_tensor(index, at::kLong, "index");
+  TORCH_CHECK(dout.dim() == 2, "dout must be [dim_size, dim]");
+  TORCH_CHECK(index.dim() == 1, "index must be [n_msg]");
+  same_device(dout, {&index});
+  const c10::OptionalDeviceGuard guard(dout.device());
+  const int64_t n = index.numel(), dim_size = dout.size(0), dim = dout.size(1);
+  at::Tensor dmsg = at::empty({n, dim}, dout.options());
+  at::Tensor bad = at::zeros({1}, index.options());
+  const size_t nb = tgnx_msg_agg_mean_bwd_ws_bytes(dim_size);
+  at::Tensor ws = ws_bytes(dout, nb);
+  check_rc(tgnx_msg_agg_mean_bwd(dout.data_ptr<float>(), index.data_ptr<int64_t>(), n, dim, dim_size,
+                                 dmsg.data_ptr<float>(), bad.data_ptr<int64_t>(), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_msg_agg_mean_bwd");
+  const int64_t nbad = bad.cpu().data_ptr<int64_t>()[0];
+  TORCH_CHECK(nbad == 0, "msg_agg_mean_bwd: ", nbad, " index entries outside [0, ", dim_size, ")");
+  return dmsg;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tgnx, m) {
@@ -414,4 +627,21 @@ TORCH_LIBRARY(tgnx, m) {
   m.def("edge_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor? e, Tensor indptr, Tensor alpha, int heads) "
         "-> (Tensor, Tensor, Tensor, Tensor)",
         &edge_attn_bwd);
+  // backward ops (tgnx/ops.py wraps them as autograd functions); need[i] = 0 skips gradient i (returned empty)
+  m.def("col_sum(Tensor x) -> Tensor", &col_sum);
+  m.def("gru_update_bwd(Tensor dh_out, Tensor x, Tensor h, Tensor w_ih, Tensor w_hh, Tensor? b_ih, Tensor? b_hh, "
+        "int cell, int[] need) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+        &gru_update_bwd);
+  m.def("predictor_bwd(Tensor dout, Tensor z_src, Tensor z_dst, Tensor w_src, Tensor? b_src, Tensor w_dst, "
+        "Tensor? b_dst, Tensor w_out, Tensor b_out, bool sigmoid, int[] need) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+        &predictor_bwd);
+  m.def("time_encode(Tensor t, Tensor w, Tensor b) -> Tensor", &time_encode);
+  m.def("time_encode_bwd(Tensor dout, Tensor t, Tensor w, Tensor b) -> (Tensor, Tensor)", &time_encode_bwd);
+  m.def("time_embedding(Tensor x, Tensor rel_t, Tensor w, Tensor b) -> Tensor", &time_embedding);
+  m.def("time_embedding_bwd(Tensor dout, Tensor x, Tensor rel_t, Tensor w, Tensor b, bool need_dx) -> "
+        "(Tensor, Tensor, Tensor)",
+        &time_embedding_bwd);
+  m.def("msg_agg_last_bwd(Tensor dout, Tensor argmax, int n_msg) -> Tensor", &msg_agg_last_bwd);
+  m.def("msg_agg_mean_bwd(Tensor dout, Tensor index) -> Tensor", &msg_agg_mean_bwd);
 }

@@ -76,6 +76,24 @@ SIGNATURES = {
                                            c_vp]),
     "tgnx_edge_attn_fwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, c_vp]),
     "tgnx_edge_attn_bwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, P, P, P, P, c_vp]),
+    # per-operator backward (tgnx_ops_bwd.hip)
+    "tgnx_col_sum_ws_bytes": (c_sz, [c_i64, c_i64]),
+    "tgnx_col_sum": (ctypes.c_int, [c_i64, c_i64, P, c_i64, P, P, c_sz, c_vp]),
+    "tgnx_memory_cell_bwd_ws_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "tgnx_memory_cell_bwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_sz,
+                                            c_vp]),
+    "tgnx_link_predictor_bwd_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "tgnx_link_predictor_bwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, P, c_i32, P, P, P, P,
+                                               P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_time_encode": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, c_vp]),
+    "tgnx_time_encode_bwd_ws_bytes": (c_sz, [c_i64, c_i64]),
+    "tgnx_time_encode_bwd": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_time_embedding": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, P, c_vp]),
+    "tgnx_time_embedding_bwd_ws_bytes": (c_sz, [c_i64, c_i64]),
+    "tgnx_time_embedding_bwd": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_msg_agg_last_bwd": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, P, c_vp]),
+    "tgnx_msg_agg_mean_bwd_ws_bytes": (c_sz, [c_i64]),
+    "tgnx_msg_agg_mean_bwd": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, P, P, P, c_sz, c_vp]),
     "tgnx_tgnn_advance": (ctypes.c_int, [P, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_u64,
                                          c_i32, c_vp]),
     "tgnx_tgnn_train_fwd_bwd": (ctypes.c_int, [P, P, c_i32, c_i32, c_vp]),

@@ -9,8 +9,12 @@ tcsr_sample (TGL t-CSR, utils.py:73), gemm_f32 (MFMA fp32 GEMM), and the TGN mod
 (csrc/tgnx_ops.hip): msg_agg_last / msg_agg_mean (LastAggregator / MeanAggregator, modules/msg_agg.py:15-26),
 gru_update (TGNMemory's GRUCell / RNNCell, memory_module.py:70-78), predictor (LinkPredictor decoder.py:12-27;
 EdgePredictor model_utils.py:165-195) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
-emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function).  No CPU fallback: loading
-needs the built library (make -C tgb-tgn-dgl_amd) and the device ops need a HIP device.
+emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function), time_encode (TimeEncoder)
+and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
+gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd, msg_agg_mean_bwd) sit
+behind the autograd functions below — memory_cell, link_predictor, time_encode, time_embedding, aggregate_last,
+aggregate_mean, linear — which tgnx/nn.py's modules call.  No CPU fallback: loading needs the built library
+(make -C tgb-tgn-dgl_amd) and the device ops need a HIP device.
 """
 from __future__ import annotations
 
@@ -21,7 +25,9 @@ import torch
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "edge_attn_fwd", "edge_attn_bwd",
-       "sample_recent", "insert_recent", "reset")
+       "sample_recent", "insert_recent", "reset",
+       "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
+       "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd")
 _loaded = False
 
 
@@ -59,3 +65,168 @@ def edge_attention(q, k, v, e, indptr, heads):
     None).  Returns (out [n_dst, H*C], alpha [E, H]); gradients flow to q, k, v, e."""
     return _EdgeAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(),
                                 None if e is None else e.contiguous(), indptr, int(heads))
+
+
+def _grads(outs, need):
+    """The backward ops return an empty tensor for a gradient that was not asked for: None to autograd."""
+    return tuple(g if n else None for g, n in zip(outs, need))
+
+
+class _Linear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return load().gemm_f32(x, weight, bias, False, True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight = ctx.saved_tensors
+        ns, dout = load(), dout.contiguous()
+        nx, nw, nb = ctx.needs_input_grad
+        dx = ns.gemm_f32(dout, weight, None, False, False) if nx else None
+        dw = None
+        if nw:  # dW = dout^T x (a contraction over the rows: zero without rows)
+            dw = ns.gemm_f32(dout, x, None, True, False) if x.size(0) else torch.zeros_like(weight)
+        db = ns.col_sum(dout) if nb and ctx.has_bias else None
+        return dx, dw, db
+
+
+def linear(x, weight, bias=None):
+    """torch.nn.functional.linear on the MFMA GEMM: x [M, in] weight^T [out, in] + bias; dx and dW by gemm_f32,
+    db by col_sum."""
+    return _Linear.apply(x.contiguous(), weight.contiguous(), None if bias is None else bias.contiguous())
+
+
+class _MemoryCell(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, h, w_ih, w_hh, b_ih, b_hh, cell):
+        ctx.save_for_backward(x, h, w_ih, w_hh, *(b for b in (b_ih, b_hh) if b is not None))
+        ctx.cell, ctx.has_b = cell, (b_ih is not None, b_hh is not None)
+        return load().gru_update(x, h, w_ih, w_hh, b_ih, b_hh, cell)
+
+    @staticmethod
+    def backward(ctx, dh_out):
+        x, h, w_ih, w_hh, *bs = ctx.saved_tensors
+        b_ih = bs.pop(0) if ctx.has_b[0] else None
+        b_hh = bs.pop(0) if ctx.has_b[1] else None
+        need = [int(n) for n in ctx.needs_input_grad[:6]]
+        need[4], need[5] = need[4] and int(ctx.has_b[0]), need[5] and int(ctx.has_b[1])
+        outs = load().gru_update_bwd(dh_out.contiguous(), x, h, w_ih, w_hh, b_ih, b_hh, ctx.cell, need)
+        return _grads(outs, need) + (None,)
+
+
+def memory_cell(x, h, w_ih, w_hh, b_ih=None, b_hh=None, cell="gru"):
+    """TGNMemory.memory_updater (memory_module.py:70-78): torch.nn.GRUCell (cell 'gru' / 0) or RNNCell with tanh
+    ('rnn' / 1) of x [M, d_in] and h [M, D] with torch's parameter layout; gradients flow to every tensor."""
+    cell = {"gru": 0, "rnn": 1}.get(cell, cell)
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    return _MemoryCell.apply(c(x), c(h), c(w_ih), c(w_hh), c(b_ih), c(b_hh), int(cell))
+
+
+class _LinkPredictor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z_src, z_dst, w_src, b_src, w_dst, b_dst, w_out, b_out, sigmoid):
+        ctx.save_for_backward(z_src, z_dst, w_src, w_dst, w_out, b_out, *(b for b in (b_src, b_dst) if b is not None))
+        ctx.sigmoid, ctx.has_b = sigmoid, (b_src is not None, b_dst is not None)
+        return load().predictor(z_src, z_dst, w_src, b_src, w_dst, b_dst, w_out, b_out, sigmoid)
+
+    @staticmethod
+    def backward(ctx, dout):
+        z_src, z_dst, w_src, w_dst, w_out, b_out, *bs = ctx.saved_tensors
+        b_src = bs.pop(0) if ctx.has_b[0] else None
+        b_dst = bs.pop(0) if ctx.has_b[1] else None
+        n = [int(v) for v in ctx.needs_input_grad[:8]]   # inputs: z_src z_dst w_src b_src w_dst b_dst w_out b_out
+        n[3], n[5] = n[3] and int(ctx.has_b[0]), n[5] and int(ctx.has_b[1])
+        # the op's order: dz_src dz_dst dw_src db_src dw_dst db_dst dw_out db_out (the same)
+        outs = load().predictor_bwd(dout.contiguous().view(-1), z_src, z_dst, w_src, b_src, w_dst, b_dst, w_out, b_out,
+                                    ctx.sigmoid, n)
+        return _grads(outs, n) + (None,)
+
+
+def link_predictor(z_src, z_dst, w_src, b_src, w_dst, b_dst, w_out, b_out, sigmoid=True):
+    """LinkPredictor (decoder.py:12-27; sigmoid) / EdgePredictor (model_utils.py:165-195; logits, z_dst rows a
+    multiple of z_src rows: row i pairs with source i mod B).  Returns [M, 1]; gradients flow to every tensor
+    (z_src's is summed over the rows that share it)."""
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    return _LinkPredictor.apply(c(z_src), c(z_dst), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out), c(b_out),
+                                bool(sigmoid))
+
+
+class _TimeEncode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, w, b):
+        ctx.save_for_backward(t, w, b)
+        return load().time_encode(t, w, b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        t, w, b = ctx.saved_tensors
+        _, nw, nb = ctx.needs_input_grad
+        if not (nw or nb):
+            return None, None, None
+        dw, db = load().time_encode_bwd(dout.contiguous(), t, w, b)
+        return None, (dw if nw else None), (db if nb else None)
+
+
+def time_encode(t, w, b):
+    """TimeEncoder: cos(w t + b) [n, D] of t [n] (fp32), w [D] or [D, 1], b [D]; the argument is the fused
+    kernels' fmaf(w, t, b) with their exact reduction.  t is data: it gets no gradient."""
+    return _TimeEncode.apply(t.contiguous(), w.contiguous(), b.contiguous())
+
+
+class _TimeEmbedding(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rel_t, w, b):
+        ctx.save_for_backward(x, rel_t, w, b)
+        return load().time_embedding(x, rel_t, w, b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, rel_t, w, b = ctx.saved_tensors
+        nx, _, nw, nb = ctx.needs_input_grad
+        dx, dw, db = load().time_embedding_bwd(dout.contiguous(), x, rel_t, w, b, bool(nx))
+        return (dx if nx else None), None, (dw if nw else None), (db if nb else None)
+
+
+def time_embedding(x, rel_t, w, b):
+    """TimeEmbedding (emb_module.py:48-50): x (1 + w rel_t + b) for x [n, D], rel_t [n] (fp32), w [D] or [D, 1],
+    b [D]; gradients flow to x, w, b."""
+    return _TimeEmbedding.apply(x.contiguous(), rel_t.contiguous(), w.contiguous(), b.contiguous())
+
+
+class _AggregateLast(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, msg, index, t, dim_size):
+        out, argmax = load().msg_agg_last(msg, index, t, dim_size)
+        ctx.save_for_backward(argmax)
+        ctx.n_msg = msg.size(0)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (argmax,) = ctx.saved_tensors
+        return load().msg_agg_last_bwd(dout.contiguous(), argmax, ctx.n_msg), None, None, None
+
+
+def aggregate_last(msg, index, t, dim_size):
+    """LastAggregator (msg_agg.py:15-21): per row of `index` the message with the largest t (the first on a tie),
+    zeros for a row without messages.  The gradient scatters back to the chosen messages."""
+    return _AggregateLast.apply(msg.contiguous(), index.contiguous(), t.contiguous(), int(dim_size))
+
+
+class _AggregateMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, msg, index, dim_size):
+        ctx.save_for_backward(index)
+        return load().msg_agg_mean(msg, index, dim_size)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (index,) = ctx.saved_tensors
+        return load().msg_agg_mean_bwd(dout.contiguous(), index), None, None
+
+
+def aggregate_mean(msg, index, dim_size):
+    """MeanAggregator (msg_agg.py:24-26): per row of `index` the mean of its messages, zeros for an empty row."""
+    return _AggregateMean.apply(msg.contiguous(), index.contiguous(), int(dim_size))
