@@ -614,6 +614,61 @@ size_t tgnx_msg_agg_mean_bwd_ws_bytes(int64_t dim_size);
 int tgnx_msg_agg_mean_bwd(const float* dout, const int64_t* index, int64_t n_msg, int64_t dim, int64_t dim_size,
                           float* dmsg, int64_t* n_invalid, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- device message store (csrc/tgnx_memstore.hip)
+ * The stores of TGNMemory / DyRepMemory (modules/memory_module.py:140-145, :180-207; DyRep :376-412) behind
+ * tgnx.nn.TGNMemory.  Times here are int64 (PyG's convention: TGNMemory keeps t and last_update as Long).
+ *   event log   src, dst, t int64[cap], raw_msg fp32[cap, msg_dim]: append-only, every batch once
+ *   node table  int64[4 N] {s_off, s_cnt, d_off, d_cnt} per node (16-B aligned; all zero = every store empty)
+ *   arena       int64[2 cap] of log slots: the batch that starts at log slot s owns entries [2s, 2s + 2B), its slots
+ *               sorted stably by src, then sorted stably by dst (a node's stored events keep batch order)
+ * The fill level lives on the host (every put's B is known there); resetting = zeroing the node table and starting
+ * again at slot 0.  Dead log entries are not compacted.  Deterministic: no float atomics. */
+
+/* _update_msg_store of both directions (memory_module.py:133-134, :180-191), one launch: appends the batch at log
+ * slots [start, start + B), fills its arena entries and points every distinct src (dst) at its new run in the s (d)
+ * store.  sorted / perm int64[2 B]: the batch's src ids sorted stably and the permutation that sorts them
+ * (indices in [0, B)), then the same for dst (torch.sort(stack([src, dst]), dim=1, stable=True)).  A node id outside
+ * [0, num_nodes) gets no run, a perm entry outside [0, B) is replaced by 0; both are counted into *n_bad (device
+ * int64, accumulated; may be NULL). */
+int tgnx_memstore_put(const int64_t* src, const int64_t* dst, const int64_t* t, const float* raw_msg, int64_t B,
+                      int64_t msg_dim, const int64_t* sorted, const int64_t* perm, int64_t start, int64_t cap,
+                      int64_t num_nodes, int64_t* log_src, int64_t* log_dst, int64_t* log_t, float* log_raw,
+                      int64_t* arena, int64_t* node_tab, int64_t* n_bad, void* stream);
+
+/* The stored events of a node set n_id[M] (no duplicates), in the order [s store of n_id[0], n_id[1], ...; d store of
+ * n_id[0], ...] (_compute_msg twice + the cat of memory_module.py:156-168), in two calls around the one size the host
+ * must know.  Both use one workspace of tgnx_memstore_gather_ws_bytes(M) bytes, which carries the scanned tile
+ * offsets from the first call to the second.
+ * count: totals (device int64[3]) = {n_s, n_d, invalid ids}: the messages of either direction and the entries of n_id
+ *   outside [0, num_nodes) plus *put_bad (the puts' count; may be NULL).  Counts are scanned on the device.
+ * gather: for message p < n_s + n_d: out_slot[p] its log slot (-1: a corrupt table entry), out_owner[p] the position
+ *   of its owner in n_id (the reference's _assoc[idx]), out_t[p] its time; out_lu[i] for i < M the max of t over node
+ *   n_id[i]'s messages of both directions, 0 without any (scatter(t, idx, reduce="max")[n_id], :176).  n_s / n_d as
+ *   count returned them; fill = log slots in use. */
+size_t tgnx_memstore_gather_ws_bytes(int64_t M);
+int tgnx_memstore_count(const int64_t* node_tab, int64_t num_nodes, const int64_t* n_id, int64_t M,
+                        const int64_t* put_bad, int64_t* totals, void* ws, size_t ws_bytes, void* stream);
+int tgnx_memstore_gather(const int64_t* node_tab, int64_t num_nodes, const int64_t* arena, const int64_t* log_t,
+                         int64_t fill, const int64_t* n_id, int64_t M, int64_t n_s, int64_t n_d, int64_t* out_slot,
+                         int64_t* out_owner, int64_t* out_t, int64_t* out_lu, const void* ws, size_t ws_bytes,
+                         void* stream);
+
+/* The message inputs of _compute_msg (memory_module.py:193-207) for the gathered slots, one wave per row:
+ * out[p] = [memory[src] | memory[dst] | raw_msg | cos(fmaf(w, t_rel, b))], width 2 mem_dim + msg_dim + time_dim, with
+ * (src, dst) = the stored event's (src, dst) for p < n_s and (dst, src) for the d store's rows, t_rel[p] = (fp32)
+ * (t - last_update[src]) taken in int64 (also written out: what tgnx_time_encode_bwd needs), the cosine with the exact
+ * argument reduction of tgnx_time_encode.  A column group moves as 16-B vectors when its offsets and widths allow and
+ * element by element otherwise.  DyRepMemory (:387-408): with emb [emb_rows, mem_dim] and emb_flags bit 0 (bit 1) an
+ * src (dst) endpoint x that is in n_id[M] takes emb[assoc[x]] instead of its memory row; x is in n_id iff
+ * stamp[x] < M and n_id[stamp[x]] == x, stamp being the node -> position map the gather's caller wrote for n_id
+ * (TGNMemory._assoc; stale entries of earlier node sets fail the second test).  emb NULL: emb_flags is ignored. */
+int tgnx_memstore_build_msg(const int64_t* slot, int64_t n_msg, int64_t n_s, const int64_t* log_src,
+                            const int64_t* log_dst, const int64_t* log_t, const float* log_raw, int64_t fill,
+                            int64_t num_nodes, int64_t mem_dim, int64_t msg_dim, int64_t time_dim, const float* memory,
+                            const int64_t* last_update, const float* w, const float* b, const float* emb,
+                            int64_t emb_rows, const int64_t* assoc, const int64_t* stamp, const int64_t* n_id, int64_t M,
+                            int32_t emb_flags, float* out, float* t_rel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

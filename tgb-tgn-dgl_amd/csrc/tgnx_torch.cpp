@@ -20,6 +20,9 @@
 //   col_sum, gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd,
 //   msg_agg_mean_bwd                         the backward halves (csrc/tgnx_ops_bwd.hip) behind tgnx/ops.py's
 //                                            autograd functions
+//   memstore_put / memstore_count / memstore_gather / memstore_build_msg
+//                                            the device message store of tgnx.nn.TGNMemory / DyRepMemory
+//                                            (memory_module.py:140-145, :180-207; csrc/tgnx_memstore.hip)
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -588,6 +591,153 @@ at::Tensor msg_agg_mean_bwd(const at::Tensor& dout, const at::Tensor& index) {
   return dmsg;
 }
 
+// ------------------------------------------------------------------ device message store (csrc/tgnx_memstore.hip)
+// The store's tensors (tgnx.nn.TGNMemory's non-persistent buffers): log_src / log_dst / log_t int64[cap], log_raw
+// fp32[cap, d], arena int64[2 cap], node_tab int64[4 N], bad int64[1].
+void store_log(const at::Tensor& log_src, const at::Tensor& log_dst, const at::Tensor& log_t,
+               const at::Tensor& log_raw) {
+  dev_tensor(log_src, at::kLong, "log_src");
+  dev_tensor(log_dst, at::kLong, "log_dst");
+  dev_tensor(log_t, at::kLong, "log_t");
+  dev_tensor(log_raw, at::kFloat, "log_raw");
+  TORCH_CHECK(log_src.dim() == 1 && log_dst.sizes() == log_src.sizes() && log_t.sizes() == log_src.sizes() &&
+                  log_raw.dim() == 2 && log_raw.size(0) == log_src.size(0),
+              "the event log must be src, dst, t [cap] and raw_msg [cap, d]");
+  same_device(log_src, {&log_dst, &log_t, &log_raw});
+}
+
+void memstore_put(const at::Tensor& src, const at::Tensor& dst, const at::Tensor& t, const at::Tensor& raw_msg,
+                  const at::Tensor& sorted, const at::Tensor& perm, int64_t start, at::Tensor log_src,
+                  at::Tensor log_dst, at::Tensor log_t, at::Tensor log_raw, at::Tensor arena, at::Tensor node_tab,
+                  at::Tensor bad) {
+  store_log(log_src, log_dst, log_t, log_raw);
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(dst, at::kLong, "dst");
+  dev_tensor(t, at::kLong, "t");
+  dev_tensor(raw_msg, at::kFloat, "raw_msg");
+  dev_tensor(sorted, at::kLong, "sorted");
+  dev_tensor(perm, at::kLong, "perm");
+  dev_tensor(arena, at::kLong, "arena");
+  dev_tensor(node_tab, at::kLong, "node_tab");
+  dev_tensor(bad, at::kLong, "bad");
+  same_device(log_src, {&src, &dst, &t, &raw_msg, &sorted, &perm, &arena, &node_tab, &bad});
+  const int64_t B = src.numel(), cap = log_src.size(0), d = log_raw.size(1);
+  TORCH_CHECK(dst.numel() == B && t.numel() == B, "src, dst, t must have the same length");
+  TORCH_CHECK(raw_msg.dim() == 2 && raw_msg.size(0) == B && raw_msg.size(1) == d, "raw_msg must be [B, ", d, "]");
+  TORCH_CHECK(sorted.numel() == 2 * B && perm.numel() == 2 * B, "sorted and perm must be [2, B]");
+  TORCH_CHECK(arena.numel() == 2 * cap, "arena must have 2 cap entries");
+  TORCH_CHECK(node_tab.numel() % 4 == 0 && bad.numel() >= 1, "node_tab must be [4 N] and bad [1]");
+  const c10::OptionalDeviceGuard guard(log_src.device());
+  check_rc(tgnx_memstore_put(src.data_ptr<int64_t>(), dst.data_ptr<int64_t>(), t.data_ptr<int64_t>(),
+                             raw_msg.data_ptr<float>(), B, d, sorted.data_ptr<int64_t>(), perm.data_ptr<int64_t>(),
+                             start, cap, node_tab.numel() / 4, log_src.data_ptr<int64_t>(),
+                             log_dst.data_ptr<int64_t>(), log_t.data_ptr<int64_t>(), log_raw.data_ptr<float>(),
+                             arena.data_ptr<int64_t>(), node_tab.data_ptr<int64_t>(), bad.data_ptr<int64_t>(),
+                             cur_stream()),
+           "tgnx_memstore_put");
+}
+
+// (totals int64[3] = {n_s, n_d, invalid ids} on the device, the workspace memstore_gather continues from): no
+// device -> host read here; the caller reads totals once to size the gather
+std::tuple<at::Tensor, at::Tensor> memstore_count(const at::Tensor& node_tab, const at::Tensor& n_id,
+                                                  const c10::optional<at::Tensor>& put_bad) {
+  dev_tensor(node_tab, at::kLong, "node_tab");
+  dev_tensor(n_id, at::kLong, "n_id");
+  TORCH_CHECK(node_tab.numel() % 4 == 0 && n_id.dim() == 1, "node_tab must be [4 N] and n_id [M]");
+  same_device(node_tab, {&n_id});
+  const int64_t* pb = nullptr;
+  if (put_bad.has_value()) {
+    dev_tensor(*put_bad, at::kLong, "put_bad");
+    TORCH_CHECK(put_bad->numel() >= 1, "put_bad must be [1]");
+    same_device(node_tab, {&*put_bad});
+    pb = put_bad->data_ptr<int64_t>();
+  }
+  const c10::OptionalDeviceGuard guard(node_tab.device());
+  const int64_t M = n_id.numel();
+  at::Tensor totals = at::empty({3}, n_id.options());
+  const size_t nb = tgnx_memstore_gather_ws_bytes(M);
+  at::Tensor ws = ws_bytes(node_tab, nb);
+  check_rc(tgnx_memstore_count(node_tab.data_ptr<int64_t>(), node_tab.numel() / 4, n_id.data_ptr<int64_t>(), M, pb,
+                               totals.data_ptr<int64_t>(), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_memstore_count");
+  return {totals, ws};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> memstore_gather(const at::Tensor& node_tab,
+                                                                           const at::Tensor& arena,
+                                                                           const at::Tensor& log_t, int64_t fill,
+                                                                           const at::Tensor& n_id, int64_t n_s,
+                                                                           int64_t n_d, const at::Tensor& ws) {
+  dev_tensor(node_tab, at::kLong, "node_tab");
+  dev_tensor(arena, at::kLong, "arena");
+  dev_tensor(log_t, at::kLong, "log_t");
+  dev_tensor(n_id, at::kLong, "n_id");
+  dev_tensor(ws, at::kByte, "ws");
+  TORCH_CHECK(node_tab.numel() % 4 == 0 && n_id.dim() == 1, "node_tab must be [4 N] and n_id [M]");
+  TORCH_CHECK(fill >= 0 && fill <= log_t.numel() && arena.numel() >= 2 * fill, "fill beyond the log's capacity");
+  TORCH_CHECK(n_s >= 0 && n_d >= 0, "n_s and n_d must be non-negative");
+  same_device(node_tab, {&arena, &log_t, &n_id, &ws});
+  const c10::OptionalDeviceGuard guard(node_tab.device());
+  const int64_t M = n_id.numel(), n = n_s + n_d;
+  auto lopt = n_id.options();
+  at::Tensor slot = at::empty({n}, lopt), owner = at::empty({n}, lopt), t = at::empty({n}, lopt);
+  at::Tensor lu = at::empty({M}, lopt);
+  check_rc(tgnx_memstore_gather(node_tab.data_ptr<int64_t>(), node_tab.numel() / 4, arena.data_ptr<int64_t>(),
+                                log_t.data_ptr<int64_t>(), fill, n_id.data_ptr<int64_t>(), M, n_s, n_d,
+                                slot.data_ptr<int64_t>(), owner.data_ptr<int64_t>(), t.data_ptr<int64_t>(),
+                                lu.data_ptr<int64_t>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+           "tgnx_memstore_gather");
+  return {slot, owner, t, lu};
+}
+
+// (rows [n_msg, 2 D + d + T], t_rel [n_msg]); emb / assoc / stamp / n_id: DyRepMemory's embeddings in messages
+std::tuple<at::Tensor, at::Tensor> memstore_build_msg(
+    const at::Tensor& slot, int64_t n_s, const at::Tensor& log_src, const at::Tensor& log_dst, const at::Tensor& log_t,
+    const at::Tensor& log_raw, int64_t fill, const at::Tensor& memory, const at::Tensor& last_update,
+    const at::Tensor& w, const at::Tensor& b, const c10::optional<at::Tensor>& emb,
+    const c10::optional<at::Tensor>& assoc, const c10::optional<at::Tensor>& stamp,
+    const c10::optional<at::Tensor>& n_id, int64_t emb_flags) {
+  store_log(log_src, log_dst, log_t, log_raw);
+  dev_tensor(slot, at::kLong, "slot");
+  dev_tensor(memory, at::kFloat, "memory");
+  dev_tensor(last_update, at::kLong, "last_update");
+  dev_tensor(w, at::kFloat, "w");
+  dev_tensor(b, at::kFloat, "b");
+  TORCH_CHECK(memory.dim() == 2 && last_update.dim() == 1 && last_update.numel() == memory.size(0),
+              "memory must be [N, D] and last_update [N]");
+  TORCH_CHECK(b.dim() == 1 && w.numel() == b.numel(), "w and b must have T entries each");
+  TORCH_CHECK(slot.dim() == 1 && n_s >= 0 && n_s <= slot.numel(), "slot must be [n_msg] and 0 <= n_s <= n_msg");
+  TORCH_CHECK(fill >= 0 && fill <= log_src.numel(), "fill beyond the log's capacity");
+  same_device(slot, {&log_src, &memory, &last_update, &w, &b});
+  const int64_t N = memory.size(0), D = memory.size(1), d = log_raw.size(1), T = b.numel(), n = slot.numel();
+  const float* pe = nullptr;
+  const int64_t *pa = nullptr, *ps = nullptr, *pn = nullptr;
+  int64_t E = 0, M = 0;
+  if (emb.has_value() && emb_flags != 0) {
+    TORCH_CHECK(assoc.has_value() && stamp.has_value() && n_id.has_value(),
+                "embeddings in messages need assoc, the stamps and n_id");
+    dev_tensor(*emb, at::kFloat, "embeddings");
+    dev_tensor(*assoc, at::kLong, "assoc");
+    dev_tensor(*stamp, at::kLong, "stamp");
+    dev_tensor(*n_id, at::kLong, "n_id");
+    TORCH_CHECK(emb->dim() == 2 && emb->size(1) == D, "embeddings must be [*, ", D, "] (the memory's width)");
+    TORCH_CHECK(assoc->numel() >= N && stamp->numel() >= N, "assoc and the stamps must have num_nodes entries");
+    same_device(slot, {&*emb, &*assoc, &*stamp, &*n_id});
+    pe = emb->data_ptr<float>(), pa = assoc->data_ptr<int64_t>(), ps = stamp->data_ptr<int64_t>();
+    pn = n_id->data_ptr<int64_t>(), E = emb->size(0), M = n_id->numel();
+  }
+  const c10::OptionalDeviceGuard guard(slot.device());
+  at::Tensor out = at::empty({n, 2 * D + d + T}, memory.options()), t_rel = at::empty({n}, memory.options());
+  check_rc(tgnx_memstore_build_msg(slot.data_ptr<int64_t>(), n, n_s, log_src.data_ptr<int64_t>(),
+                                   log_dst.data_ptr<int64_t>(), log_t.data_ptr<int64_t>(), log_raw.data_ptr<float>(),
+                                   fill, N, D, d, T, memory.data_ptr<float>(), last_update.data_ptr<int64_t>(),
+                                   w.data_ptr<float>(), b.data_ptr<float>(), pe, E, pa, ps, pn, M,
+                                   (int32_t)(pe ? emb_flags : 0), out.data_ptr<float>(), t_rel.data_ptr<float>(),
+                                   cur_stream()),
+           "tgnx_memstore_build_msg");
+  return {out, t_rel};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tgnx, m) {
@@ -644,4 +794,17 @@ TORCH_LIBRARY(tgnx, m) {
         &time_embedding_bwd);
   m.def("msg_agg_last_bwd(Tensor dout, Tensor argmax, int n_msg) -> Tensor", &msg_agg_last_bwd);
   m.def("msg_agg_mean_bwd(Tensor dout, Tensor index) -> Tensor", &msg_agg_mean_bwd);
+  // device message store (tgnx.nn.TGNMemory / DyRepMemory)
+  m.def("memstore_put(Tensor src, Tensor dst, Tensor t, Tensor raw_msg, Tensor sorted, Tensor perm, int start, "
+        "Tensor(a!) log_src, Tensor(b!) log_dst, Tensor(c!) log_t, Tensor(d!) log_raw, Tensor(e!) arena, "
+        "Tensor(f!) node_tab, Tensor(g!) bad) -> ()",
+        &memstore_put);
+  m.def("memstore_count(Tensor node_tab, Tensor n_id, Tensor? put_bad=None) -> (Tensor, Tensor)", &memstore_count);
+  m.def("memstore_gather(Tensor node_tab, Tensor arena, Tensor log_t, int fill, Tensor n_id, int n_s, int n_d, "
+        "Tensor ws) -> (Tensor, Tensor, Tensor, Tensor)",
+        &memstore_gather);
+  m.def("memstore_build_msg(Tensor slot, int n_s, Tensor log_src, Tensor log_dst, Tensor log_t, Tensor log_raw, "
+        "int fill, Tensor memory, Tensor last_update, Tensor w, Tensor b, Tensor? emb=None, Tensor? assoc=None, "
+        "Tensor? stamp=None, Tensor? n_id=None, int emb_flags=0) -> (Tensor, Tensor)",
+        &memstore_build_msg);
 }

@@ -94,6 +94,14 @@ SIGNATURES = {
     "tgnx_msg_agg_last_bwd": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, P, c_vp]),
     "tgnx_msg_agg_mean_bwd_ws_bytes": (c_sz, [c_i64]),
     "tgnx_msg_agg_mean_bwd": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, P, P, P, c_sz, c_vp]),
+    # device message store (tgnx_memstore.hip)
+    "tgnx_memstore_put": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, P, P, c_i64, c_i64, c_i64, P, P, P, P, P, P, P,
+                                         c_vp]),
+    "tgnx_memstore_gather_ws_bytes": (c_sz, [c_i64]),
+    "tgnx_memstore_count": (ctypes.c_int, [P, c_i64, P, c_i64, P, P, P, c_sz, c_vp]),
+    "tgnx_memstore_gather": (ctypes.c_int, [P, c_i64, P, P, c_i64, P, c_i64, c_i64, c_i64, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_memstore_build_msg": (ctypes.c_int, [P, c_i64, c_i64, P, P, P, P, c_i64, c_i64, c_i64, c_i64, c_i64, P, P, P,
+                                               P, P, c_i64, P, P, P, c_i64, c_i32, P, P, c_vp]),
     "tgnx_tgnn_advance": (ctypes.c_int, [P, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_u64,
                                          c_i32, c_vp]),
     "tgnx_tgnn_train_fwd_bwd": (ctypes.c_int, [P, P, c_i32, c_i32, c_vp]),

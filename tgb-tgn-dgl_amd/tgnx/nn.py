@@ -12,14 +12,22 @@ autograd functions of tgnx/ops.py (HIP kernels forward and backward; no eager-Py
     GraphAttentionEmbedding(in, out, msg_dim, time_enc)  modules/emb_module.py:11-29
     TimeEmbedding(in, out)                             modules/emb_module.py:32-52 (JODIE's projection)
     LinkPredictor(in_channels)                         modules/decoder.py:12-27
+    TGNMemory(num_nodes, raw_msg_dim, memory_dim, time_dim, message_module, aggregator_module,
+              memory_updater_cell='gru')               modules/memory_module.py:25-215
+    DyRepMemory(..., memory_updater_type, use_src_emb_in_msg=False, use_dst_emb_in_msg=False)
+                                                       modules/memory_module.py:218-421
 
-Constructing a module and calling state_dict() needs neither a GPU nor the built library; forward needs both
-(the parameters and inputs on the HIP device).  Plumbing stays in torch: torch.cat, the gathers x[index] and the
-edge sort.  A gather's backward is torch's index_add, the one part of a composed step whose summation order is
-not fixed.  A stateful TGNMemory with a device message store is not provided here (the fused engine owns one).
+Constructing a module (the two memories and their stores included) and calling state_dict() needs neither a GPU
+nor the built library; forward, update_state, train(False) and message_store need both (the module and its inputs
+on the HIP device).  Plumbing stays in torch: torch.cat, the gathers x[index], the row writes memory[n_id] = ...,
+the edge sort and the stable sort of a stored batch's node ids.  A gather's backward is torch's index_add, the one
+part of a composed step whose summation order is not fixed.  The memories keep their message stores on the device
+(csrc/tgnx_memstore.hip): putting a batch, gathering the stored events of a node set and building the message rows
+are HIP launches with no per-node host work.
 """
 from __future__ import annotations
 
+import copy
 import math
 
 import torch
@@ -188,5 +196,209 @@ class LinkPredictor(nn.Module):
                                   self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, sigmoid=True)
 
 
+class TGNMemory(nn.Module):
+    """modules/memory_module.py:25-215 over a device message store (csrc/tgnx_memstore.hip).
+
+    Submodules and buffers carry the reference's names (msg_s_module, msg_d_module — a deep copy —, aggr_module,
+    time_enc, memory_updater; memory [N, D] f32, last_update [N] int64, _assoc [N] int64), so a reference state dict
+    loads with strict=True.  The stores are non-persistent buffers (they follow .to(device) and stay out of the state
+    dict, as the reference's dicts do): an append-only event log _log_src / _log_dst / _log_t int64[cap], _log_raw
+    f32[cap, d] that holds each batch once, the node table _node_tab int64[4 N] {s_off, s_cnt, d_off, d_cnt} and the
+    arena _arena int64[2 cap] of log slots.  The fill level is a host integer; the log grows geometrically;
+    reset_state() and the flush of train(False) rewind it.  Dead entries are not compacted within an epoch.
+
+    t and last_update are int64 (PyG's convention), raw_msg f32; t_rel = t - last_update[src] is taken in int64 and
+    then cast.  A node's stored events keep batch order; messages are ordered [msg_s of n_id[0], n_id[1], ...;
+    msg_d of n_id[0], ...]; LastAggregator's ties go to the first message in that order.  n_id must be
+    free of duplicates, as in the reference's loop (forward's callers pass a unique() result).
+
+    forward(n_id) reads one size from the device (the message count, to allocate the rows); the aggregation op
+    keeps its own index check.  update_state's store update runs without any host synchronisation.
+    `message_module` is called as (z_src, z_dst, raw_msg, t_enc) -> [n_msg, out_channels] on four column views of
+    one buffer the build kernel writes; IdentityMessage takes that buffer as its output without a torch.cat.
+    `aggregator_module` is called as (msg, index, t, dim_size)."""
+
+    _FLUSH_CHUNK = 1 << 18  # train(False): nodes per memory(n_id) pass (bounds the [chunk, out_channels] rows)
+
+    def __init__(self, num_nodes: int, raw_msg_dim: int, memory_dim: int, time_dim: int, message_module: nn.Module,
+                 aggregator_module: nn.Module, memory_updater_cell: str = "gru", store_capacity: int = 4096):
+        super().__init__()
+        self.num_nodes, self.raw_msg_dim, self.memory_dim, self.time_dim = num_nodes, raw_msg_dim, memory_dim, time_dim
+        self.use_src_emb_in_msg = self.use_dst_emb_in_msg = False
+        self.msg_s_module = message_module
+        self.msg_d_module = copy.deepcopy(message_module)
+        self.aggr_module = aggregator_module
+        self.time_enc = TimeEncoder(time_dim)
+        self.memory_updater = MemoryCell(message_module.out_channels, memory_dim, memory_updater_cell)
+        self.register_buffer("memory", torch.empty(num_nodes, memory_dim))
+        self.register_buffer("last_update", torch.empty(num_nodes, dtype=torch.long))
+        self.register_buffer("_assoc", torch.zeros(num_nodes, dtype=torch.long))
+        cap =max(int(store_capacity), 1)
+        for name in ("_log_src", "_log_dst", "_log_t"):
+            self.register_buffer(name, torch.zeros(cap, dtype=torch.long), persistent=False)
+        self.register_buffer("_log_raw", torch.zeros(cap, raw_msg_dim), persistent=False)
+        self.register_buffer("_arena", torch.zeros(2 * cap, dtype=torch.long), persistent=False)
+        self.register_buffer("_node_tab", torch.zeros(4 * num_nodes, dtype=torch.long), persistent=False)
+        self.register_buffer("_store_bad", torch.zeros(1, dtype=torch.long), persistent=False)
+        self._fill = 0
+        self.reset_parameters()
+
+    @property
+    def device(self) -> torch.device:
+        return self.time_enc.lin.weight.device
+
+    def reset_parameters(self):
+        for m in (self.msg_s_module, self.msg_d_module, self.aggr_module):
+            if hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+        self.time_enc.reset_parameters()
+        self.memory_updater.reset_parameters()
+        self.reset_state()
+
+    def reset_state(self):
+        """memory = 0, last_update = 0, both stores empty, the arena rewound."""
+        self.memory.zero_()
+        self.last_update.zero_()
+        self._reset_message_store()
+
+    def _reset_message_store(self):
+        self._node_tab.zero_()
+        self._store_bad.zero_()
+        self._fill = 0
+
+    def detach(self):
+        self.memory.detach_()
+
+    def forward(self, n_id):
+        if self.training:
+            return self._get_updated_memory(n_id)
+        return self.memory[n_id], self.last_update[n_id]
+
+    def update_state(self, src, dst, t, raw_msg):
+        self._update_state(src, dst, t, raw_msg, None, None)
+
+    def _update_state(self, src, dst, t, raw_msg, embeddings, assoc):
+        n_id = torch.cat([src, dst]).unique()
+        if self.training:
+            self._update_memory(n_id, embeddings, assoc)
+            self._update_msg_store(src, dst, t, raw_msg)
+        else:
+            self._update_msg_store(src, dst, t, raw_msg)
+            self._update_memory(n_id, embeddings, assoc)
+
+    @torch.no_grad()
+    def _update_memory(self, n_id, embeddings=None, assoc=None):
+        memory, last_update = self._get_updated_memory(n_id, embeddings, assoc)
+        self.memory[n_id] = memory
+        self.last_update[n_id] = last_update
+
+    def _gather(self, n_id):
+        """(slot, owner, t [n_s + n_d], last_update [M], n_s): tgnx_memstore_count, the one size read,
+        tgnx_memstore_gather."""
+        ns = ops.load()
+        totals, ws = ns.memstore_count(self._node_tab, n_id, self._store_bad)
+        n_s, n_d, bad = totals.tolist()
+        if bad:
+            raise IndexError(f"TGNMemory: {bad} node ids outside [0, {self.num_nodes}) in n_id or in stored batches")
+        slot, owner, t, lu = ns.memstore_gather(self._node_tab, self._arena, self._log_t, self._fill, n_id, n_s, n_d, ws)
+        return slot, owner, t, lu, n_s
+
+    def _get_updated_memory(self, n_id, embeddings=None, assoc=None):
+        n_id = n_id.contiguous()
+        M = n_id.numel()
+        self._assoc[n_id] = torch.arange(M, device=n_id.device)
+        slot, owner, t, last_update, n_s = self._gather(n_id)
+        flags = 0
+        if embeddings is not None:
+            flags = int(self.use_src_emb_in_msg) | (int(self.use_dst_emb_in_msg) << 1)
+        emb = (embeddings.detach().contiguous(), assoc.contiguous(), self._assoc, n_id) if flags else (None,) * 4
+        buf = ops.build_messages(self.time_enc.lin.weight, self.time_enc.lin.bias, slot, n_s, self._log_src,
+                                 self._log_dst, self._log_t, self._log_raw, self._fill, self.memory, self.last_update,
+                                 *emb, emb_flags=flags)
+        if isinstance(self.msg_s_module, IdentityMessage) and isinstance(self.msg_d_module, IdentityMessage):
+            msg = buf
+        else:
+            D, d = self.memory_dim, self.raw_msg_dim
+            cols = (buf[:, :D], buf[:, D:2 * D], buf[:, 2 * D:2 * D + d], buf[:, 2 * D + d:])
+            msg = torch.cat([self.msg_s_module(*(c[:n_s] for c in cols)),
+                             self.msg_d_module(*(c[n_s:] for c in cols))], dim=0)
+        aggr = self.aggr_module(msg, owner, t, M)
+        memory = self.memory_updater(aggr, self.memory[n_id])
+        return memory, last_update
+
+    @torch.no_grad()
+    def _update_msg_store(self, src, dst, t, raw_msg):
+        """_update_msg_store of both directions (memory_module.py:133-134): a stable sort of the batch's node ids,
+        then one launch.  No host synchronisation."""
+        B = src.numel()
+        if B == 0:
+            return
+        if self._fill + B > self._log_src.numel():
+            self._grow(self._fill + B)
+        keys, perm = torch.sort(torch.stack([src, dst]), dim=1, stable=True)
+        ops.load().memstore_put(src.contiguous(), dst.contiguous(), t.contiguous(), raw_msg.contiguous(), keys, perm,
+                                self._fill, self._log_src, self._log_dst, self._log_t, self._log_raw, self._arena,
+                                self._node_tab, self._store_bad)
+        self._fill += B
+
+    def _grow(self, need: int):
+        """Geometric growth by plain reallocation (arena entries are absolute log slots: they survive the move)."""
+        cap = self._log_src.numel()
+        while cap < need:
+            cap *= 2
+        f = self._fill
+        for name, n in (("_log_src", f), ("_log_dst", f), ("_log_t", f), ("_log_raw", f), ("_arena", 2 * f)):
+            old = getattr(self, name)
+            new = old.new_zeros((2 * cap if name == "_arena" else cap,) + tuple(old.shape[1:]))
+            new[:n] = old[:n]
+            setattr(self, name, new)
+
+    @torch.no_grad()
+    def message_store(self, direction: str = "s"):
+        """(count [N] int64, src, dst, t, raw_msg): the stored events of direction 's' (a node's events as src) or
+        'd' (as dst), concatenated in node order; as in the reference's stores `src` is the owning node in both."""
+        if direction not in ("s", "d"):
+            raise ValueError("direction must be 's' or 'd'")
+        n_id = torch.arange(self.num_nodes, device=self._node_tab.device)
+        slot, _, t, _, n_s = self._gather(n_id)
+        tab = self._node_tab.view(self.num_nodes, 4)
+        if direction == "s":
+            sel, count = slot[:n_s], tab[:, 1].clone()
+            return count, self._log_src[sel], self._log_dst[sel], t[:n_s], self._log_raw[sel]
+        sel, count = slot[n_s:], tab[:, 3].clone()
+        return count, self._log_dst[sel], self._log_src[sel], t[n_s:], self._log_raw[sel]
+
+    def train(self, mode: bool = True):
+        if self.training and not mode:
+            # flush every node's store into memory (every row from the pre-flush state), then empty the stores
+            N, C = self.num_nodes, self._FLUSH_CHUNK
+            with torch.no_grad():
+                rows = [self._get_updated_memory(torch.arange(i, min(i + C, N), device=self.memory.device))
+                        for i in range(0, N, C)]
+                if rows:
+                    self.memory.copy_(torch.cat([r[0] for r in rows]) if len(rows) > 1 else rows[0][0])
+                    self.last_update.copy_(torch.cat([r[1] for r in rows]) if len(rows) > 1 else rows[0][1])
+            self._reset_message_store()
+        return super().train(mode)
+
+
+class DyRepMemory(TGNMemory):
+    """modules/memory_module.py:218-421: TGNMemory with the updater cell named memory_updater_type and, with
+    use_src_emb_in_msg / use_dst_emb_in_msg, update_state(..., embeddings, assoc) building its messages with
+    embeddings[assoc[x]] in place of the memory row of a source / destination endpoint x that is in the batch's node
+    set (:387-408).  Membership is tested on the device against the stamps in _assoc.  The embeddings are data: they
+    enter under no_grad.  assoc must map every such x to a row of `embeddings`."""
+
+    def __init__(self, num_nodes: int, raw_msg_dim: int, memory_dim: int, time_dim: int, message_module: nn.Module,
+                 aggregator_module: nn.Module, memory_updater_type: str, use_src_emb_in_msg: bool = False,
+                 use_dst_emb_in_msg: bool = False, store_capacity: int = 4096):
+        super().__init__(num_nodes, raw_msg_dim, memory_dim, time_dim, message_module, aggregator_module,
+                         memory_updater_type, store_capacity)
+        self.use_src_emb_in_msg, self.use_dst_emb_in_msg = bool(use_src_emb_in_msg), bool(use_dst_emb_in_msg)
+
+    def update_state(self, src, dst, t, raw_msg, embeddings=None, assoc=None):
+        self._update_state(src, dst, t, raw_msg, embeddings, assoc)
+
+
 __all__ = ["TimeEncoder", "IdentityMessage", "LastAggregator", "MeanAggregator", "MemoryCell", "TransformerConv",
-           "GraphAttentionEmbedding", "TimeEmbedding", "LinkPredictor"]
+           "GraphAttentionEmbedding", "TimeEmbedding", "LinkPredictor", "TGNMemory", "DyRepMemory"]

@@ -13,7 +13,10 @@ emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd functi
 and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
 gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd, msg_agg_mean_bwd) sit
 behind the autograd functions below — memory_cell, link_predictor, time_encode, time_embedding, aggregate_last,
-aggregate_mean, linear — which tgnx/nn.py's modules call.  No CPU fallback: loading needs the built library
+aggregate_mean, linear — which tgnx/nn.py's modules call.  memstore_put / memstore_count / memstore_gather /
+memstore_build_msg (csrc/tgnx_memstore.hip) are the device message store of tgnx.nn.TGNMemory / DyRepMemory
+(memory_module.py:140-145, :180-207); `build_messages` below is memstore_build_msg with the time encoder's
+gradient.  No CPU fallback: loading needs the built library
 (make -C tgb-tgn-dgl_amd) and the device ops need a HIP device.
 """
 from __future__ import annotations
@@ -27,7 +30,8 @@ OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "t
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "edge_attn_fwd", "edge_attn_bwd",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
-       "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd")
+       "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
+       "memstore_put", "memstore_count", "memstore_gather", "memstore_build_msg")
 _loaded = False
 
 
@@ -230,3 +234,33 @@ class _AggregateMean(torch.autograd.Function):
 def aggregate_mean(msg, index, dim_size):
     """MeanAggregator (msg_agg.py:24-26): per row of `index` the mean of its messages, zeros for an empty row."""
     return _AggregateMean.apply(msg.contiguous(), index.contiguous(), int(dim_size))
+
+
+class _BuildMessages(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, b, slot, n_s, log_src, log_dst, log_t, log_raw, fill, memory, last_update, emb, assoc, stamp,
+                n_id, emb_flags):
+        buf, t_rel = load().memstore_build_msg(slot, n_s, log_src, log_dst, log_t, log_raw, fill, memory, last_update,
+                                               w, b, emb, assoc, stamp, n_id, emb_flags)
+        ctx.save_for_backward(t_rel, w, b)
+        ctx.te0 = buf.size(1) - b.numel()
+        return buf
+
+    @staticmethod
+    def backward(ctx, dbuf):
+        t_rel, w, b = ctx.saved_tensors
+        nw, nb = ctx.needs_input_grad[:2]
+        dw = db = None
+        if nw or nb:
+            dw, db = load().time_encode_bwd(dbuf[:, ctx.te0:].contiguous(), t_rel, w, b)
+        return (dw if nw else None, db if nb else None) + (None,) * 14
+
+
+def build_messages(w, b, slot, n_s, log_src, log_dst, log_t, log_raw, fill, memory, last_update, emb=None, assoc=None,
+                   stamp=None, n_id=None, emb_flags=0):
+    """The message inputs of TGNMemory._compute_msg (memory_module.py:193-207) for gathered store slots, one
+    buffer [n_msg, 2 D + d + T] = [memory[src] | memory[dst] | raw_msg | cos(w t_rel + b)] (tgnx_memstore_build_msg).
+    The memory, raw-message and (DyRep) embedding columns are data; the time-encoding columns carry the gradient
+    to w and b through time_encode_bwd with the saved t_rel."""
+    return _BuildMessages.apply(w.contiguous(), b.contiguous(), slot, int(n_s), log_src, log_dst, log_t, log_raw,
+                                int(fill), memory, last_update, emb, assoc, stamp, n_id, int(emb_flags))
