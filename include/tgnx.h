@@ -354,6 +354,14 @@ typedef struct {
  * update parameters and moments without storing the gradient in buf->grads (the batch loss slot
  * grads[P] is still written); for loops that never read the gradients (the benchmark, the drop-in train()) */
 #define TGNX_TGN_NO_GRAD_STORE 1
+/* tgnx_tgn_train_step_pp at 1 hop with LastAggregator, the GRU cell and TGNMemory messages gathers the NEXT batch's
+ * parameter-free message rows (tgn_agg_emit's root / edge records, msg and memory columns, accumulator zeroing)
+ * inside its fixup launch, and writes memory / last_update one launch earlier; the next step then starts with the
+ * short tgn_enc_fill launch (the time-encoding columns from its own te_w / te_b) instead of tgn_agg_emit.  The
+ * message columns of the next batch are therefore copied out of the memory table before the step returns: a
+ * caller that rewrites memory / last_update / the stores between two prefetched steps must issue the next step
+ * with prefetched = 0.  This bit keeps the step on tgn_agg_emit (every other step form always is). */
+#define TGNX_TGN_NO_GATHER_AHEAD 2
 /* exchanged memory row, all fields floats holding exact integers so that the row survives a SUM exchange
  * (one all-reduce over [gradients | every rank's row slots, zero but the sender's] is the all-gather):
  * node (-1 = unused slot; num_nodes < 2^24), last_update bits 0-23, 24-47, 48-63, memory[D] */

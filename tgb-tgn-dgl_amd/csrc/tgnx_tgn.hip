@@ -66,7 +66,7 @@ constexpr int TB_MAX = 4095; // events per batch (12-bit event index in the touc
 #define TGNX_DXE_DR TGNX_G32L_DR  // direct-operand slabs per round of the dX_enc GEMM (the 7-wave dW_cell launch)
 #endif
 using GXE = GemmCfg<TGNX_G32L_T, TGNX_G32L_T, TGNX_G32L_KC, TGNX_G32L_PF, TGNX_G32L_WS, TGNX_DXE_DR>;
-enum { CNT_R = 0, CNT_M = 1, CNT_E = 2, CNT_U = 3, CNT_LIST = 6, CNT_NB = 9, CNT_WORDS = 16 };  // (4, 5: unused)
+enum { CNT_R = 0, CNT_M = 1, CNT_E = 2, CNT_U = 3, CNT_LIST = 6, CNT_NB = 9, CNT_GNB = 10, CNT_WORDS = 16 };  // (4, 5: unused)
 // ctl[ERR] bit of a step that found its scan-output set holding another batch (tgnx_tgn_train_step_pp)
 constexpr int64_t ERR_STALE_SET = 16;
 constexpr int64_t ERR_SORT_CAP = 32;  // edge_sort_body: more sampled rows than its LDS counters (host-checked; never expected)
@@ -211,6 +211,7 @@ struct Ctx {
   int *e_j, *e_c;
   int64_t* e_id;
   float* e_t;
+  float* e_dt;  // [Ecap] gather-ahead steps: the sampled edge's Δt (GatherJob -> tgn_enc_fill)
   float *X, *trel, *lu;
   int* evr;  // [3 B] centre row of each root (src, dst, neg) of this rank's events (tgn_agg_emit)
   int4* evq;  // [3 B] 1 hop: per root {centre row, P row, edge range} (tgn_pred_train<ATT>); nullptr at 2 hops
@@ -359,17 +360,19 @@ struct ResDesc {
   int64_t start, seed;
   int B, lo, hi, gen;
 };
-__device__ __forceinline__ ResDesc res_desc(const Ctx& c, int ahead) {
+// (ctl: the counters to derive it from — the live words, or SnapJob's copy of them)
+__device__ __forceinline__ ResDesc res_desc_at(const Ctx& c, const int64_t* ctl, int ahead) {
   ResDesc d;
-  const int64_t nb = c.ctl[TGNX_CTL_NB] + ahead;
+  const int64_t nb = ctl[TGNX_CTL_NB] + ahead;
   d.start = c.adv_lo + nb * c.adv_batch;
   d.B = d.start >= c.adv_hi ? 0 : (int)min(c.adv_hi - d.start, c.adv_batch);
   d.lo = (int)((int64_t)d.B * c.adv_rank / c.adv_world);
   d.hi = (int)((int64_t)d.B * (c.adv_rank + 1) / c.adv_world);
   d.seed = (int64_t)(mix64(c.adv_seed ^ mix64((uint64_t)(nb + 1))) >> 1);
-  d.gen = (int)c.ctl[TGNX_CTL_GEN] + 1 + ahead;
+  d.gen = (int)ctl[TGNX_CTL_GEN] + 1 + ahead;
   return d;
 }
+__device__ __forceinline__ ResDesc res_desc(const Ctx& c, int ahead) { return res_desc_at(c, c.ctl, ahead); }
 // the descriptor words of batch d into ctl, for the launches after this one
 __device__ __forceinline__ void write_desc(const Ctx& c, const ResDesc& d) {
   c.ctl[TGNX_CTL_BATCH_START] = d.start;
@@ -1202,7 +1205,9 @@ __device__ __forceinline__ const float* msg_row(const Ctx& c, int64_t v, bool se
 }
 // AG: the aggregation compiled in (0 last, 1 mean, -1 either by c.aggr): the last-only kernel does not carry
 // the mean path's registers (233 -> fewer VGPRs: more tgn_agg_emit workgroups resident at once)
-template <int AG, bool EMB = false>
+// ENC = false (the gather half of a gather-ahead step, GatherJob): everything but the Δt-encoding columns of X and
+// s0m / s1m, which need this step's te_w / te_b (tgn_enc_fill writes them from trel / xw)
+template <int AG, bool EMB = false, bool ENC = true>
 __device__ void agg_node(const Ctx& c, int64_t n, int m, int lane, bool grad) {
   const int D = c.D, d = c.d, Qm = c.Qm, enc0 = 2 * D + d;
   const StoreView sv = store_view(c, n);
@@ -1211,7 +1216,7 @@ __device__ void agg_node(const Ctx& c, int64_t n, int m, int lane, bool grad) {
   const float* P = c.params;
   if (tot == 0) {
     for (int k = lane; k < Qm; k += 64) X[k] = 0.f;
-    if (grad)
+    if (grad && ENC)
       for (int q = lane; q < D; q += 64) c.s0m[(int64_t)m * D + q] = c.s1m[(int64_t)m * D + q] = 0.f;
     if (lane == 0) {
       c.xw[m] = -1;
@@ -1258,8 +1263,9 @@ __device__ void agg_node(const Ctx& c, int64_t n, int m, int lane, bool grad) {
         const int k = k0 + 64 * i;
         if (k >= Qm) continue;
         const bool enc = k >= enc0;
+        if (!ENC && enc) continue;
         float cs = 0.f;
-        if (enc) {
+        if (ENC && enc) {
           const int q = k - enc0;
           float sn;
           te_sincos(fmaf(P[c.L.te_w + q], tr, P[c.L.te_b + q]), sn, cs);
@@ -1636,6 +1642,108 @@ __device__ void zero_bwd_acc(const Ctx& c, int64_t t, int64_t nt) {
     for (int rp = 0; rp < c.dzrep; ++rp) zero_span(c.dZc + rp * c.dzstride, (int64_t)R * c.HC, t, nt);
   }
 }
+// root records of events [lo, hi) of the batch at `start`, as block bid of nevb 256-thread blocks: the centre row of
+// every root of this rank's events, so that tgn_pred_train starts from one index load (root_row: assoc -> rank)
+__device__ __forceinline__ void agg_root_part(const Ctx& c, int lo, int hi, int64_t start, int bid, int nevb) {
+  if (c.evj) {  // 16 lanes per root: its record and its edges' neighbour rows (ring slot order, valid
+                // slots compacted: the e_j of its edge range), so the attention in tgn_pred_train<ATT>
+                // reads q, skip and every k / v / edge row in its second round
+    const int sl = threadIdx.x & 15, K = c.K;
+    for (int x = (bid * blockDim.x + threadIdx.x) >> 4; x < 3 * (hi - lo); x += (nevb * blockDim.x) >> 4) {
+      const int i = lo + x / 3, r = x % 3;
+      const int64_t* src = r == 0 ? c.ev_src : r == 1 ? c.ev_dst : c.neg;
+      const int64_t v = src[start + i];
+      const int a = (int)c.assoc[v];
+      const int64_t e = c.eid[v * K + min(sl, K - 1)], u = c.nbr[v * K + min(sl, K - 1)];
+      const bool ok = sl < K && e >= 0;
+      const uint32_t m = (uint32_t)(__ballot(ok) >> (threadIdx.x & 48)) & 0xFFFFu;
+      const int xr = c.crank[a];
+      const int ju = (int)c.assoc[ok ? u : v];
+      if (ok) {
+        const int idx = __popc(m & ((1u << sl) - 1u));
+        c.evj[x * 16 + idx] = ju;
+        c.cevj[xr * 16 + idx] = ju;
+      }
+      if (sl == 0) {
+        const int e0 = c.ceoff[xr], e1 = c.ceoff[xr + 1];
+        c.evr[x] = xr;
+        c.evq[x] = make_int4(xr, a, e0, e1);
+        c.cevq[xr] = make_int4(a, e0, e1, 0);
+      }
+    }
+    return;
+  }
+  for (int x = bid * blockDim.x + threadIdx.x; x < 3 * (hi - lo); x += nevb * blockDim.x) {
+    const int i = lo + x / 3, r = x % 3;
+    const int64_t* src = r == 0 ? c.ev_src : r == 1 ? c.ev_dst : c.neg;
+    if (c.evq) {  // 1 hop: the root's centre row, its P row and edge range (one round for the attention)
+      const int a = (int)c.assoc[src[start + i]], xr = c.crank[a];
+      c.evr[x] = xr;
+      c.evq[x] = make_int4(xr, a, c.ceoff[xr], c.ceoff[xr + 1]);
+    } else {
+      c.evr[x] = root_row(c, src[start + i]);
+    }
+  }
+}
+// the sampled-edge part as block bid of nedge: a wave per (centre, ring slot).
+// ENC = false (mode 0, the gather half of a gather-ahead step): the record and the msg columns of the edge's row,
+// and its Δt into e_dt; tgn_enc_fill writes the cos columns with the step's own te_w / te_b
+template <bool ENC>
+__device__ __forceinline__ void agg_edge_part(const Ctx& c, int mode, int bid, int nedge, int lane) {
+  const int R = c.cnt[CNT_R], K = c.K, D = c.D;
+  const float* tw = c.params + c.L.te_w;
+  const float* tb = c.params + c.L.te_b;
+  for (int pr = bid * 4 + (threadIdx.x >> 6); pr < R * K; pr += nedge * 4) {
+    const int x = pr / K, j = pr - x * K;
+    const int64_t v = c.cent[x];
+    const int ls = min(lane, K - 1);
+    const int64_t e_l = c.eid[v * K + ls];
+    const int64_t u_l = c.nbr[v * K + ls];
+    const float t_l = c.rt[v * K + ls];
+    const uint64_t valid = __ballot(lane < K && e_l >= 0);
+    if (!((valid >> j) & 1ull)) continue;
+    const int o = c.ceoff[x] + __popcll(valid & ((1ull << j) - 1ull));
+    const int64_t e = shfl_i64(e_l, j), u = shfl_i64(u_l, j);
+    const float te = lane_f(t_l, j);
+    const int ju = (int)c.assoc[u];
+    const float lu = mode == 0 ? store_tmax(c, u, lane) : (float)c.lu_buf[u];
+    const float dt = lu - te;
+    if (lane == 0) {
+      c.e_j[o] = ju;
+      c.e_c[o] = x;
+      c.e_id[o] = e;
+      c.e_t[o] = te;
+      if (!ENC) c.e_dt[o] = dt;
+    }
+    if (c.x2r && lane == 1) {  // 2 hops: a root's edges are its outer edges, same slot order
+      const int x1 = c.x2r[x];
+      if (x1 >= 0) {
+        const int o1 = c.ceoff1[x1] + (o - c.ceoff[x]);
+        c.e1_j[o1] = c.crank[ju];
+        c.e1_e2[o1] = o;
+        c.e1_id[o1] = e;
+      }
+    }
+    if (mode == 0) {  // train: the edge's whole lin_edge operand row [cos enc | msg] (stride D + d), so the
+                      // lin_edge / dW_edge GEMMs read dense rows (no event-id gather round per K chunk)
+      const int d = c.d, DA = D + d;
+      float* row = c.encE + (int64_t)o * DA;
+      const float* msg = c.ev_msg + e * d;
+      float mv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) mv[i] = msg[min(lane + 64 * i, max(d - 1, 0))];  // (loads before the sincos)
+      // (the backward recomputes the sine from the same argument, EpiTeEdge: no [E][D] sine round trip)
+      if (ENC)
+        for (int q = lane; q < D; q += 64) row[q] = te_cos(fmaf(tw[q], dt, tb[q]));
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (lane + 64 * i < d) row[D + lane + 64 * i] = mv[i];
+      for (int q = lane + 256; q < d; q += 64) row[D + q] = msg[q];
+    } else {
+      for (int q = lane; q < D; q += 64) c.encE[(int64_t)o * D + q] = te_cos(fmaf(tw[q], dt, tb[q]));
+    }
+  }
+}
 #ifndef TGNX_AGG_WAVES
 #define TGNX_AGG_WAVES 0  // waves-per-SIMD floor of tgn_agg_emit (0: the compiler's register count)
 #endif
@@ -1655,106 +1763,15 @@ __global__ void __launch_bounds__(256) TGNX_AGG_ATTR tgn_agg_emit(Ctx c, int mod
     if (B == 0 || c.ctl[TGNX_CTL_ERR] != 0) return;
   }
   const int lane = threadIdx.x & 63;
-  if ((int)blockIdx.x < nevb) {  // train: the centre row of every root of this rank's events, so that
-                                 // tgn_pred_train starts from one index load (root_row: assoc -> rank)
-    const int lo = (int)c.ctl[TGNX_CTL_LO], hi = (int)c.ctl[TGNX_CTL_HI];
-    const int64_t start = c.ctl[TGNX_CTL_BATCH_START];
-    if (c.evj) {  // 16 lanes per root: its record and its edges' neighbour rows (ring slot order, valid
-                  // slots compacted: the e_j of its edge range), so the attention in tgn_pred_train<ATT>
-                  // reads q, skip and every k / v / edge row in its second round
-      const int sl = threadIdx.x & 15, K = c.K;
-      for (int x = (blockIdx.x * blockDim.x + threadIdx.x) >> 4; x < 3 * (hi - lo); x += (nevb * blockDim.x) >> 4) {
-        const int i = lo + x / 3, r = x % 3;
-        const int64_t* src = r == 0 ? c.ev_src : r == 1 ? c.ev_dst : c.neg;
-        const int64_t v = src[start + i];
-        const int a = (int)c.assoc[v];
-        const int64_t e = c.eid[v * K + min(sl, K - 1)], u = c.nbr[v * K + min(sl, K - 1)];
-        const bool ok = sl < K && e >= 0;
-        const uint32_t m = (uint32_t)(__ballot(ok) >> (threadIdx.x & 48)) & 0xFFFFu;
-        const int xr = c.crank[a];
-        const int ju = (int)c.assoc[ok ? u : v];
-        if (ok) {
-          const int idx = __popc(m & ((1u << sl) - 1u));
-          c.evj[x * 16 + idx] = ju;
-          c.cevj[xr * 16 + idx] = ju;
-        }
-        if (sl == 0) {
-          const int e0 = c.ceoff[xr], e1 = c.ceoff[xr + 1];
-          c.evr[x] = xr;
-          c.evq[x] = make_int4(xr, a, e0, e1);
-          c.cevq[xr] = make_int4(a, e0, e1, 0);
-        }
-      }
-      return;
-    }
-    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < 3 * (hi - lo); x += nevb * blockDim.x) {
-      const int i = lo + x / 3, r = x % 3;
-      const int64_t* src = r == 0 ? c.ev_src : r == 1 ? c.ev_dst : c.neg;
-      if (c.evq) {  // 1 hop: the root's centre row, its P row and edge range (one round for the attention)
-        const int a = (int)c.assoc[src[start + i]], xr = c.crank[a];
-        c.evr[x] = xr;
-        c.evq[x] = make_int4(xr, a, c.ceoff[xr], c.ceoff[xr + 1]);
-      } else {
-        c.evr[x] = root_row(c, src[start + i]);
-      }
-    }
+  if ((int)blockIdx.x < nevb) {
+    agg_root_part(c, (int)c.ctl[TGNX_CTL_LO], (int)c.ctl[TGNX_CTL_HI], c.ctl[TGNX_CTL_BATCH_START], blockIdx.x, nevb);
     return;
   }
   // then the node part (its workgroups run longest: hub nodes' stores), the sampled-edge part in the last
   // nedge blocks; both loop over their runtime work in strides of their block count
   const int nnode = gridDim.x - nedge - nevb;
   if ((int)blockIdx.x >= nevb + nnode) {
-    const int R = c.cnt[CNT_R], K = c.K, D = c.D;
-    const float* tw = c.params + c.L.te_w;
-    const float* tb = c.params + c.L.te_b;
-    for (int pr = ((int)blockIdx.x - nevb - nnode) * 4 + (threadIdx.x >> 6); pr < R * K; pr += nedge * 4) {
-      const int x = pr / K, j = pr - x * K;
-      const int64_t v = c.cent[x];
-      const int ls = min(lane, K - 1);
-      const int64_t e_l = c.eid[v * K + ls];
-      const int64_t u_l = c.nbr[v * K + ls];
-      const float t_l = c.rt[v * K + ls];
-      const uint64_t valid = __ballot(lane < K && e_l >= 0);
-      if (!((valid >> j) & 1ull)) continue;
-      const int o = c.ceoff[x] + __popcll(valid & ((1ull << j) - 1ull));
-      const int64_t e = shfl_i64(e_l, j), u = shfl_i64(u_l, j);
-      const float te = lane_f(t_l, j);
-      const int ju = (int)c.assoc[u];
-      const float lu = mode == 0 ? store_tmax(c, u, lane) : (float)c.lu_buf[u];
-      if (lane == 0) {
-        c.e_j[o] = ju;
-        c.e_c[o] = x;
-        c.e_id[o] = e;
-        c.e_t[o] = te;
-      }
-      if (c.x2r && lane == 1) {  // 2 hops: a root's edges are its outer edges, same slot order
-        const int x1 = c.x2r[x];
-        if (x1 >= 0) {
-          const int o1 = c.ceoff1[x1] + (o - c.ceoff[x]);
-          c.e1_j[o1] = c.crank[ju];
-          c.e1_e2[o1] = o;
-          c.e1_id[o1] = e;
-        }
-      }
-      const float dt = lu - te;
-      if (mode == 0) {  // train: the edge's whole lin_edge operand row [cos enc | msg] (stride D + d), so the
-                        // lin_edge / dW_edge GEMMs read dense rows (no event-id gather round per K chunk)
-        const int d = c.d, DA = D + d;
-        float* row = c.encE + (int64_t)o * DA;
-        const float* msg = c.ev_msg + e * d;
-        float mv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mv[i] = msg[min(lane + 64 * i, max(d - 1, 0))];  // (loads before the sincos)
-        // (the backward recomputes the sine from the same argument, EpiTeEdge: no [E][D] sine round trip)
-        for (int q = lane; q < D; q += 64) row[q] = te_cos(fmaf(tw[q], dt, tb[q]));
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (lane + 64 * i < d) row[D + lane + 64 * i] = mv[i];
-        for (int q = lane + 256; q < d; q += 64) row[D + q] = msg[q];
-      } else {
-        for (int q = lane; q < D; q += 64) c.encE[(int64_t)o * D + q] = te_cos(fmaf(tw[q], dt, tb[q]));
-      }
-    }
+    agg_edge_part<true>(c, mode, (int)blockIdx.x - nevb - nnode, nedge, lane);
     return;
   }
   const int bid = blockIdx.x - nevb, nb = nnode;
@@ -1782,6 +1799,83 @@ __global__ void __launch_bounds__(256) TGNX_AGG_ATTR tgn_agg_emit(Ctx c, int mod
   for (int m = bid * 4 + (threadIdx.x >> 6); m < n; m += nb * 4) {
     const int64_t v = mode == 0 ? c.nid[m] : (list ? list[m] : base + m);
     agg_node<AG, EMB>(c, v, m, lane, mode == 0);
+  }
+}
+
+// Gather-ahead steps (tgnx_tgn_train_step_pp, 1 hop, LastAggregator, GRU, TGNMemory messages): tgn_agg_emit's
+// mode-0 work in two halves.  Everything that does not read a parameter — root records, edge records with the msg
+// columns of encE and Δt per edge (e_dt), the [mem_n | mem_other | raw] columns of X with xw / trel / lu, the zeroing
+// of the backward accumulators — is this job: it reads only state that is final before the previous step's fixup
+// launch (ring, stores, the other parity's scan outputs, negatives, memory / last_update moved to the dW_cell
+// launch), so it rides there as workgroups of that launch, for the batch one past the snapshot counters (ahead;
+// from the snapshot's words: the live descriptor is rewritten by that launch).  ahead = 0: the same as a launch of its
+// own after tgn_mark + tgn_scan (a step that was not prefetched), from the live descriptor.
+// It tags the set with the batch ordinal it gathered for (CNT_GNB), checked by tgn_enc_fill beside the scan's tag.
+struct GatherJob {
+  int ahead, nevb, nnode, nedge;
+  // c: the set to gather for; ctl: the words the descriptor comes from
+  __device__ __forceinline__ void operator()(const Ctx& c, const int64_t* ctl, int bid) const {
+    int B, lo, hi;
+    int64_t start, nb;
+    if (ahead) {
+      const ResDesc d = res_desc_at(c, ctl, 1);
+      B = d.B, lo = d.lo, hi = d.hi, start = d.start;
+      nb = ctl[TGNX_CTL_NB] + 1;
+    } else {
+      B = (int)ctl[TGNX_CTL_B], lo = (int)ctl[TGNX_CTL_LO], hi = (int)ctl[TGNX_CTL_HI];
+      start = ctl[TGNX_CTL_BATCH_START];
+      nb = ctl[TGNX_CTL_NB];
+    }
+    // no next batch, an error, or a set that does not hold that batch's scan: nothing (the tag stays stale)
+    if (B == 0 || *c.errw != 0 || c.cnt[CNT_NB] != (int)nb) return;
+    if (bid == 0 && threadIdx.x == 0) c.cnt[CNT_GNB] = (int)nb;
+    const int lane = threadIdx.x & 63;
+    if (bid < nnode) {  // (first: hub nodes' stores are the longest chains)
+      zero_bwd_acc(c, bid * (int64_t)blockDim.x + threadIdx.x, (int64_t)nnode * blockDim.x);
+      const int M = c.cnt[CNT_M];
+      for (int m = bid * 4 + (threadIdx.x >> 6); m < M; m += nnode * 4) agg_node<0, false, false>(c, c.nid[m], m, lane, true);
+    } else if (bid < nnode + nedge) {
+      agg_edge_part<false>(c, 0, bid - nnode, nedge, lane);
+    } else {
+      agg_root_part(c, lo, hi, start, bid - nnode - nedge, nevb);
+    }
+  }
+};
+__global__ void __launch_bounds__(256) tgn_gather(Ctx c, GatherJob j) { j(c, c.ctl, (int)blockIdx.x); }
+
+// The other half, first launch of a gather-ahead step: the Δt-encoding columns from this step's te_w / te_b — a wave
+// per row; sampled edge o: encE[o][:D] = cos(w e_dt[o] + b); sampled node m with a message: X[m][enc0:] = cos,
+// s0m / s1m = sin, sin Δt of (w trel[m] + b) (a node without one keeps the zeros the gather wrote) — with the
+// expressions of agg_node / agg_edge_part, so both paths give the same bits.  It makes the step's stale-set check.
+__global__ void __launch_bounds__(256) tgn_enc_fill(Ctx c) {
+  const int B = (int)c.ctl[TGNX_CTL_B], nb = (int)c.ctl[TGNX_CTL_NB];
+  const bool stale = c.cnt[CNT_NB] != nb || c.cnt[CNT_GNB] != nb;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && B > 0 && stale) c.ctl[TGNX_CTL_ERR] |= ERR_STALE_SET;
+  if (B == 0 || stale || c.ctl[TGNX_CTL_ERR] != 0) return;
+  const int E = c.cnt[CNT_E], M = c.cnt[CNT_M], D = c.D, lane = threadIdx.x & 63, enc0 = 2 * D + c.d;
+  const float* tw = c.params + c.L.te_w;
+  const float* tb = c.params + c.L.te_b;
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < E + M; r += gridDim.x * 4) {
+    if (r < M) {
+      const int m = r;
+      const bool has = c.xw[m] >= 0;
+      const float tr = c.trel[m];
+      float* X = c.X + (int64_t)m * c.Qm + enc0;
+      for (int q = lane; q < D; q += 64) {
+        float sn = 0.f, cs = 0.f;
+        if (has) {
+          te_sincos(fmaf(tw[q], tr, tb[q]), sn, cs);
+          X[q] = cs;
+        }
+        c.s0m[(int64_t)m * D + q] = sn;
+        c.s1m[(int64_t)m * D + q] = sn * tr;
+      }
+    } else {
+      const int o = r - M;
+      const float dt = c.e_dt[o];
+      float* row = c.encE + (int64_t)o * (D + c.d);
+      for (int q = lane; q < D; q += 64) row[q] = te_cos(fmaf(tw[q], dt, tb[q]));
+    }
   }
 }
 
@@ -4123,10 +4217,14 @@ __global__ void __launch_bounds__(256) tgn_update(Ctx c, int nmem, int nst, int 
 
 // the message-store half of update_state, riding in the launch before the fixup (dW_gru ‖ dX_enc):
 // nothing after tgn_agg_emit reads the stores
+// nmem > 0 (gather-ahead steps): the memory / last_update half too, as its first blocks (from the step's live
+// descriptor and update list), so that the next batch's GatherJob in the fixup launch reads the updated tables.  No
+// job of the dW_cell launch reads them: the GRU's dW_cell operand is the dense Hp copy (LoadGruAT1H), EpiTeEdge
+// reads the per-sample c.lu
 struct StoreJob {
   Ctx c;
-  int nst;
-  __device__ void operator()(int bid, float*) const { update_body(c, bid, 0, nst, 0, nullptr, nullptr, 0, 0); }
+  int nst, nmem;
+  __device__ void operator()(int bid, float*) const { update_body(c, bid, nmem, nst, 0, c.upd, c.cnt + CNT_U, 0, 0); }
 };
 // One block in the same launch: copies what the fixup reads of the step descriptor (ctl words, counts,
 // update list) for fixup_view — the pipelined step's next-batch scan runs inside the fixup launch and
@@ -4184,11 +4282,23 @@ struct ScanJob {
 // wdesc (tgnx_tgn_train_step_pp, whose next batch was scanned earlier in the step): the first Δt block also
 // advances the step counters and writes the next batch's descriptor into the live ctl (nothing in this
 // launch reads them: te.c is the snapshot)
+// GA (gather-ahead steps): the first ngat tail blocks are the next batch's GatherJob (dispatched first in the launch:
+// they are its longest dependent chains, the fixup tiles fill in behind them); nmem = 0 there (StoreJob::nmem, a launch earlier)
+template <bool GA = false>
 struct TrainTail {
   TeReduceTail te;
   Ctx nxt;
   int nscan, nte, nmem, wdesc;
+  GatherJob gat;
+  int ngat;
   __device__ __forceinline__ void operator()(int bid, float* smem) const {
+    if constexpr (GA) {
+      if (bid < ngat) {  // (nxt = the other parity's set; the descriptor from the snapshot counters)
+        gat(nxt, te.c.ctl, bid);
+        return;
+      }
+      bid -= ngat;
+    }
     if (bid < nscan) scan_body<true, NoCheckpoint, 512>(nxt, bid, reinterpret_cast<unsigned char*>(smem), NoCheckpoint{}, 0, true);
     else if ((bid -= nscan) < nte) {
       if (wdesc && bid == 0 && threadIdx.x == 0) {  // (te.c reads the snapshot: nothing here reads these words)
@@ -4362,7 +4472,7 @@ static GemmShape shp_dWe2(const Caps& k, const int* cnt) { return gemm_shape_spl
 static GemmShape shp_dWlp(const Caps& k, const int* cnt) { return gemm_shape_split<GW>(2 * k.D, k.D, 3 * k.B, nullptr, nullptr, cnt ? cnt + CNT_LIST : nullptr, std::max(TGNX_S_LP, std::min(64, (3 * k.B + 63) / 64))); }
 static GemmShape shp_dWg(const Caps& k, const int* cnt) { return gemm_shape_split<GW>(k.G * k.D, k.Qm + k.D + 1, k.Mtr, nullptr, nullptr, cnt ? cnt + CNT_M : nullptr, std::min(TGNX_DWG_SMAX, ksplit(k.Mtr, TGNX_S_WG))); }
 struct WsLay {
-  size_t cb, nb, cbs, nbs, cl, nl, rbs, rl, kval, cnt, cent, cent_loc, ceoff, crank, upd_loc, nid, upd, e_j, e_c, kj, kx, ke, e_id, e_t, X, trel, lu, xw, gates, Z0, P,
+  size_t cb, nb, cbs, nbs, cl, nl, rbs, rl, kval, cnt, cent, cent_loc, ceoff, crank, upd_loc, nid, upd, e_j, e_c, kj, kx, ke, e_id, e_t, e_dt, X, trel, lu, xw, gates, Z0, P,
       Ep, alpha, alk, Qo, Zc, Hp, evs, evr, evq, evj, cevq, cevj, Hs, Hd, dZc, dP, dE, dKV, dG, tgp, encE, s0m, s1m, pA, pB, pC, pD, rkeys, rruns, skeys, sruns, pcnt,
       snap, rb, x2r, cent1, r_x2, ceoff1, e1_j, e1_e2, e1_id, P2, Ep2, alpha1, Zr, dZr, dP2, dE2, pE, pF,
       uX, uZ, uG, ulu, uxw, utrel, total;
@@ -4400,6 +4510,7 @@ static WsLay make_ws(const tgnx_tgn_config* cfg, const Caps& k) {
   W.ke = carve(off, (size_t)k.Etr * 4);
   W.e_id = carve(off, (size_t)k.Ecap * 8);
   W.e_t = carve(off, (size_t)k.Ecap * 4);
+  W.e_dt = carve(off, (size_t)k.Ecap * 4);
   W.X = carve(off, (size_t)k.Mcap * k.Qm * 4);
   W.trel = carve(off, (size_t)k.Mcap * 4);
   W.lu = carve(off, (size_t)k.Mcap * 4);
@@ -4592,6 +4703,7 @@ static int make_ctx(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* b, int K
   c.ke = reinterpret_cast<int*>(ws + W.ke);
   c.e_id = reinterpret_cast<int64_t*>(ws + W.e_id);
   c.e_t = reinterpret_cast<float*>(ws + W.e_t);
+  c.e_dt = reinterpret_cast<float*>(ws + W.e_dt);
   c.X = reinterpret_cast<float*>(ws + W.X);
   c.trel = reinterpret_cast<float*>(ws + W.trel);
   c.lu = reinterpret_cast<float*>(ws + W.lu);
@@ -4763,6 +4875,24 @@ static Ctx root_view(const Ctx& c) {
 #endif
 #ifndef TGNX_AGG_NODE_CAP
 #define TGNX_AGG_NODE_CAP 512
+#endif
+#ifndef TGNX_GA_FIRST
+#define TGNX_GA_FIRST 1  // gather-ahead: the GatherJob blocks before (1) or after (0) the fixup tiles in their launch (after: ±0,
+                         // 0.0794 / 0.0794 vs 0.0792-0.0794 ms, profiles/r7/r7_caps2_ab.txt)
+#endif
+// grid caps of the GatherJob's edge / node parts.  Smaller than tgn_agg_emit's: the gather shares its launch with the
+// fixup tiles, and with 1024 / 512 the launch has ~2,000 workgroups against ~1,500 resident at once (76 VGPRs, 22 KB of
+// LDS: 6 per CU) — read as: the tiles queued behind the gather (not traced).  Same-box A/B, ms per step (parent 0.0835): 1024 / 512 0.0812 /
+// 0.0814, 512 / 256 0.0792-0.0794, 512 / 128 0.0792 / 0.0794, 384 / 128 0.0794 / 0.0796, 256 / 128 0.0812 / 0.0817
+// (profiles/r7/r7_caps_ab.txt, r7_caps2_ab.txt)
+#ifndef TGNX_GA_EDGE_CAP
+#define TGNX_GA_EDGE_CAP 512
+#endif
+#ifndef TGNX_GA_NODE_CAP
+#define TGNX_GA_NODE_CAP 256
+#endif
+#ifndef TGNX_ENC_CAP
+#define TGNX_ENC_CAP 2048  // grid cap of tgn_enc_fill (4 rows per workgroup)
 #endif
 // the attention backward for a ring of K and the predictor's dZc copy count (compile-time: the copies' loads batched)
 using AttnBwdFn = void (*)(Ctx, int, int, int, Ctx);
@@ -5058,12 +5188,27 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
     TGNX_LAUNCH_CHECK("tgn_scan");
   }
   const int nedge = gridn((int64_t)kr.Rtr * c.K, 4, TGNX_AGG_EDGE_CAP);
-  probe_begin(TGNX_K_EDGE_META, s);
   const int nevb = gridn(3 * kr.B * (c.evj ? 16 : 1), 256);
   const int nagg = nevb + nedge + gridn(kr.Mtr, 4, TGNX_AGG_NODE_CAP);
+  // gather-ahead (GatherJob): the parameter-free half of tgn_agg_emit ran in the previous step's fixup launch (or
+  // runs here, for a step that was not prefetched); tgn_enc_fill adds the Δt-encoding columns
+  const bool ga = CELL == 0 && ppm && fuse_adam && k.layers == 1 && c.aggr == 0 && !c.emb && !c.xrows &&
+                  !(buf->flags & TGNX_TGN_NO_GATHER_AHEAD);
+  const int ngn = gridn(kr.Mtr, 4, TGNX_GA_NODE_CAP), nge = gridn((int64_t)kr.Rtr * c.K, 4, TGNX_GA_EDGE_CAP);
+  const GatherJob gat{1, nevb, ngn, nge};
+  const int ngat = nevb + ngn + nge;
+  if (ga && pipe != 1) {
+    GatherJob g0 = gat;
+    g0.ahead = 0;
+    launch_k(tgn_gather, dim3(ngat), dim3(256), 0, s, c, g0);
+    TGNX_LAUNCH_CHECK("tgn_gather");
+  }
+  probe_begin(TGNX_K_EDGE_META, s);
   const int64_t* nol = nullptr;
   const int* noc = nullptr;
-  if (c.aggr == 0)
+  if (ga)
+    launch_k(tgn_enc_fill, dim3(gridn(kr.Etr + kr.Mtr, 4, TGNX_ENC_CAP)), dim3(256), 0, s, c);
+  else if (c.aggr == 0)
     launch_k(tgn_agg_emit<0>, dim3(nagg), dim3(256), 0, s, c, 0, nedge, nol, noc, 0, (int64_t)0, nevb);
   else if (c.aggr == 1 && c.d <= 192)
     launch_k(tgn_agg_emit<1>, dim3(nagg), dim3(256), 0, s, c, 0, nedge, nol, noc, 0, (int64_t)0, nevb);
@@ -5253,7 +5398,9 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
   // first workgroups when it fits their LDS, else its own launch after it
   const auto j_scan = BlockJob<ScanJob, 3 * MARK_LDS_WORDS>{ScanJob{cn}, walk_bwd ? 0 : plans_pred || c.ptab ? 1 : 1 + 2 * c.pplan};
   const auto j_snap = BlockJob<SnapJob>{SnapJob{c, ppm ? 1 : 0}, 1};
-  const auto j_store = BlockJob<StoreJob>{StoreJob{c, nst}, nst};
+  const int nmem = gridn(kr.Ucap, 4, 1024);
+  const int nmem7 = ga ? nmem : 0;  // (gather-ahead: the memory / last_update half rides here, not in the fixup)
+  const auto j_store = BlockJob<StoreJob>{StoreJob{c, nst, nmem7}, nst + nmem7};
   // (the scan may ride in the dz0 launch instead: TGNX_SCAN_AT 6)
   const bool scan6 = scan_w3 && TGNX_SCAN_AT == 6;
   const bool walk_w3 = (scan_w3 || plans_pred) && !walk_bwd;  // (the walk rides in the dW_cell launch)
@@ -5286,13 +5433,17 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
   // step descriptor from SnapJob's copy (cf) — so that the pipelined step's next-batch scan (counters
   // advanced by SnapJob) rides in the same launch as its first workgroups when it fits (scan_folds)
   const int nte = (2 * D + 63) / 64;
-  const int nmem = gridn(kr.Ucap, 4, 1024);
   const bool scan_next = pipe && !no_tail && !ppm;
   const bool fold = scan_next && scan_folds(c, k, kr);
   const int nscan = fold ? 1 + 2 * c.pplan : 0;
-  const TrainTail tail{TeReduceTail{cf, rows_edge, rows_msg}, c, nscan, nte, nmem, ppm ? 1 : 0};
+  const TrainTail<false> tail{TeReduceTail{cf, rows_edge, rows_msg}, c, nscan, nte, nmem, ppm ? 1 : 0, gat, 0};
   probe_begin(TGNX_K_FINISH, s);
-  if (two)
+  if (ga) {  // the next batch's gather first in the launch, on the other parity's set
+    const TrainTail<true> tga{TeReduceTail{cf, rows_edge, rows_msg}, cn, 0, nte, 0, 1, gat, ngat};
+    gemm_fixup_launch_h(TGNX_GA_FIRST ? ngat : 0, ngat + nte, tga, s, gemm_fix<GW>(shp_dWe(kr, cf.cnt), c.pA, e_dWe),
+                        gemm_fix<GW>(shp_dWp(kr, cf.cnt), c.pB, e_dWp), gemm_fix<GW>(shp_dWlp(kr, cf.cnt), c.pC, e_dWlp),
+                        gemm_fix<GW>(shp_dWg(kr, cf.cnt), c.pD, e_dWg));
+  } else if (two)
     gemm_fixup_launch_h(nscan, nscan + nte + nmem, tail, s, gemm_fix<GW>(shp_dWe(kr, cf.cnt), c.pA, e_dWe),
                         gemm_fix<GW>(shp_dWp(kr, cf.cnt), c.pB, e_dWp), gemm_fix<GW>(shp_dWlp(kr, cf.cnt), c.pC, e_dWlp),
                         gemm_fix<GW>(shp_dWg(kr, cf.cnt), c.pD, e_dWg),

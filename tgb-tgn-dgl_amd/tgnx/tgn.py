@@ -231,10 +231,25 @@ class TGNModel(nn.Module):
         f = self._tgnx_finish() if getattr(self, "_tgnx_finish", None) is not None else None
         if f is not None:
             f()
+        self.invalidate_prefetch()   # (the caller may go on to write the tensors it reads: state_dict() returns the buffers)
+
+    def invalidate_prefetch(self) -> None:
+        """Tell the bound engine that memory / last_update / the stores may have been rewritten behind it: its next
+        resident step prepares its batch again instead of using what the previous step gathered ahead
+        (TgnEngine.gather_ahead)."""
+        f = self._tgnx_invalidate() if getattr(self, "_tgnx_invalidate", None) is not None else None
+        if f is not None:
+            f()
 
     def state_dict(self, *a, **k):
         self.settle()
         return super().state_dict(*a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self.settle()
+        out = super().load_state_dict(*a, **k)
+        self.invalidate_prefetch()
+        return out
 
     def forward(self, *a, **k):
         raise RuntimeError("tgnx TGN runs through tgnx.tgn.TgnEngine / pyg_epoch_utils (the fused HIP step)")
@@ -307,7 +322,14 @@ class TgnEngine:
     step k + 1 (tgnx_tgn_train_fwd_bwd_pp).  Between such steps memory, last_update, the parameters and the
     Adam moments are one apply behind: call finish() before reading them directly.  check(), loss_sum(),
     flush(), eval / reset / binding calls and model.state_dict() do so themselves (the gradient buffer is final
-    once the step's exchange returned: the apply does not change it)."""
+    once the step's exchange returned: the apply does not change it).
+
+    Gather-ahead (gather_ahead, default on; world-1 parity-set steps at 1 hop with LastAggregator, the GRU cell and
+    TGNMemory messages): a prefetched step also copies the NEXT batch's message rows out of memory / last_update /
+    the stores, inside its last launch.  Every other engine call, a loader version change, model.load_state_dict(),
+    model.settle() / state_dict() and model.invalidate_prefetch() make the next step prepare its batch again.  A raw
+    tensor write to memory / last_update / the stores between two resident steps without one of these is seen by the
+    GRU's hidden-state operand but not by the pre-gathered message rows: call invalidate_prefetch() after it."""
 
     def __init__(self, model: TGNModel, loader, events: dict, optimizer: TgnAdam | None = None,
                  dst_nodes=None, seed: int = 0, rank: int = 0, world: int = 1, data_parallel: bool | None = None):
@@ -315,6 +337,7 @@ class TgnEngine:
         self.dev = model.device
         import weakref
         model._tgnx_finish = weakref.WeakMethod(self.finish)   # model.settle(): the deferred apply, if any
+        model._tgnx_invalidate = weakref.WeakMethod(self.invalidate_prefetch)
         cfg = model.cfg
         if cfg.ring != loader.size:
             cfg.ring = loader.size
@@ -353,6 +376,10 @@ class TgnEngine:
         # (bench.py, the drop-in train()) set False before bind_resident: TGNX_TGN_NO_GRAD_STORE, 1.1 MB of
         # stores less per wiki-shaped step.  Data-parallel steps always write it (it is the exchange).
         self.keep_grads = True
+        # parity-set steps gather the next batch's parameter-free message rows inside their fixup launch and start
+        # with tgn_enc_fill instead of tgn_agg_emit (include/tgnx.h TGNX_TGN_NO_GATHER_AHEAD; the class docstring has
+        # the rule for raw writes to memory between steps).  Set before bind_resident; False keeps tgn_agg_emit.
+        self.gather_ahead = True
         # resident steps fold the batch cursor into the step's first launch: tgnx_tgn_train_step_resident
         # (world 1, Adam fused) or tgnx_tgn_train_fwd_bwd_resident (world > 1; exchange + update follow).
         # Both forms are tested against advance + step per rank (test_gpu_tgn.py, test_gpu_tgn_dp.py).
@@ -436,7 +463,7 @@ class TgnEngine:
         b.xrows, b.xcap = _p(self.xrows), (0 if self.xrows is None else self.xcap)
         b.out_ev = _p(self.out_ev)
         b.plan_table = _p(self.plan_table)
-        b.flags = 0 if self.keep_grads else 1   # TGNX_TGN_NO_GRAD_STORE
+        b.flags = (0 if self.keep_grads else 1) | (0 if self.gather_ahead else 2)   # TGNX_TGN_NO_GRAD_STORE, _NO_GATHER_AHEAD
         # steps on these buffers leave grad_flat stale (fused Adam without the store; data-parallel steps always
         # write it: it heads the exchange buffer)
         m._grads_stale = not self.keep_grads and not self.dp
@@ -444,6 +471,10 @@ class TgnEngine:
 
     def _stream(self):
         return _lib.stream(self.dev)
+
+    def invalidate_prefetch(self):
+        """The next resident step marks, scans and gathers its batch itself (model.invalidate_prefetch)."""
+        self._prefetched = False
 
     def advance(self, batch_start: int, B: int, train: bool):
         self.finish()
