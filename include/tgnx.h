@@ -154,6 +154,9 @@ int64_t tgnx_stamps_count(void);
                                    descriptor already holds the NEXT batch when its update runs */
 #define TGNX_CTL_APPLY 17       /* TGNN resident world-1 step: Adam step count of the update still to apply
                                    (tgnx_tgnn_train_step_resident defers it to the next step's first launch), 0: none */
+#define TGNX_CTL_EVAL_NB 18     /* tgnx_tgn_eval_step_resident: eval batches stepped since the pass began (its own cursor:
+                                   a validation pass between two train epochs leaves the train cursor's rule as
+                                   tgnx_tgnn_advance has it, NB += 1 per batch) */
 #define TGNX_CTL_WORDS 24
 
 #define TGNX_TGNN_NPARAM 15     /* te_w te_b attn_l attn_r attn_e Wn bn We be Ws bs Wd bd Wo bo */
@@ -497,6 +500,23 @@ int tgnx_tgn_train_update(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* bu
  * batch-start memory and ring, per-event reciprocal rank in buf->mrr, then update_state in eval
  * order (store, then GRU update) and the ring insert. */
 int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t Kn, void* stream);
+/* The resident form of tgnx_tgn_eval_step: a validation / test pass over events [split_lo, split_hi) in batches of
+ * `batch` with no host work between batches.  The batch comes from the device cursor ctl[TGNX_CTL_EVAL_NB] (batch nb
+ * = events [split_lo + nb * batch, ...), the last one partial, a step past the end a no-op with B = 0), which this
+ * call advances together with GEN / NB (as tgnx_tgnn_advance with train = 0 does; ADAM_T untouched); set the cursor
+ * word to 0 to begin a pass.  No argument changes from batch to batch, so one captured HIP graph serves the split.
+ * buf->neg is the split's negatives table int64 [split_hi - split_lo, Kn] (row e - split_lo = event e's negatives);
+ * rr_ev is double [split_hi - split_lo]: event e's reciprocal rank is written to rr_ev[e - split_lo] (buf->mrr[i],
+ * out_pos / out_neg hold the last batch, as after tgnx_tgn_eval_step).  rank / world / base_seed fill the
+ * descriptor's LO / HI / SEED words only: every rank evaluates the whole batch.
+ * The marking is deduplicated: each distinct candidate node's ring row is walked once per batch instead of once per
+ * candidate slot (two launches, tgn_eval_claim + tgn_mark_eval, for tgn_mark<false>); the sampled sets, and every
+ * launch after the scan, are those of tgnx_tgn_eval_step, and so are the results, bit for bit.
+ * Test: tests/test_gpu_tgn_eval_resident.py (against the per-batch step, the oracle at 999 negatives, and the
+ * duplicate-candidate cases on both bitmap branches). */
+int tgnx_tgn_eval_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
+                                int64_t split_hi, int64_t batch, int32_t Kn, int32_t rank, int32_t world,
+                                uint64_t base_seed, double* rr_ev, void* stream);
 /* train(False): update the memory of every node from its stored messages, clear the stores
  * (memory_module.py:209-215).  Every row is computed from the pre-flush state (:212 updates arange(N) at
  * once).  Graphs with more nodes than the workspace's GRU row capacity run in chunks that read a snapshot

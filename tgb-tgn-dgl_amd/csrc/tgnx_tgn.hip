@@ -550,6 +550,162 @@ __global__ void __launch_bounds__(256) tgn_mark(Ctx c, int nmark) {
   mark_body<TRAIN>(c, blockIdx.x, nmark, 0, lbm);
 }
 
+// ------------------------------------------------------------------ resident eval pass (tgnx_tgn_eval_step_resident)
+// The batch cursor of the resident eval step: tgnn_advance mode 1 with train = 0 restated over the eval cursor
+// word (the train forms' cursor is TGNX_CTL_NB itself; an eval pass between two train epochs keeps its own), so
+// no host argument changes from batch to batch.  GEN / NB advance as a tgnx_tgnn_advance per batch advances them.
+// A step past the end of the split (B = 0): mark and scan return at once, so the cursor clears the scan's counts —
+// the launches after the scan size their work from them, and the previous batch's would run its update again.
+__global__ void tgn_eval_cursor(int64_t* ctl, int* cnt, int64_t split_lo, int64_t split_hi, int64_t batch, int rank,
+                                int world, uint64_t base_seed) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int64_t nb = ctl[TGNX_CTL_EVAL_NB];
+  const int64_t start = split_lo + nb * batch;
+  const int64_t B = start >= split_hi ? 0 : min(split_hi - start, batch);
+  if (B == 0) cnt[CNT_R] = cnt[CNT_M] = cnt[CNT_E] = cnt[CNT_U] = cnt[CNT_LIST] = cnt[CNT_R1] = cnt[CNT_E1] = 0;
+  ctl[TGNX_CTL_BATCH_START] = start;
+  ctl[TGNX_CTL_B] = B;
+  ctl[TGNX_CTL_STEP_B] = B;
+  ctl[TGNX_CTL_CUR_EID] = start;
+  ctl[TGNX_CTL_GEN] += 1;
+  ctl[TGNX_CTL_NB] += 1;
+  ctl[TGNX_CTL_EVAL_NB] = nb + 1;
+  ctl[TGNX_CTL_LO] = B * rank / world;
+  ctl[TGNX_CTL_HI] = B * (rank + 1) / world;
+  ctl[TGNX_CTL_SEED] = (int64_t)(mix64(base_seed ^ mix64((uint64_t)ctl[TGNX_CTL_NB])) >> 1);
+}
+// the batch's reciprocal ranks (tgn_score: mrr[i]) to their event rows of the pass's table
+__global__ void tgn_eval_rr(const int64_t* ctl, const double* mrr, double* rr_ev, int64_t split_lo) {
+  const int B = (int)ctl[TGNX_CTL_B];
+  if (B == 0 || ctl[TGNX_CTL_ERR] != 0) return;
+  const int64_t o = ctl[TGNX_CTL_BATCH_START] - split_lo;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B; i += gridDim.x * blockDim.x) rr_ev[o + i] = mrr[i];
+}
+
+// Deduplicated eval marking.  tgn_mark<false> walks the ring row of every candidate slot (B (2 + Kn) of them: 200k at
+// 200 x 999) although a TGB batch has ~1,000 distinct candidates; every write of the walk is idempotent (the same
+// kval, bits going 0 -> 1), so all but one walk per node are repeated work.  Two launches, no atomics for the choice:
+//   tgn_eval_claim  every slot stores its index into own[v] (plain stores; the last one stays) and stamps node_gen of
+//                   the src / dst entries (per slot, as tgn_mark does);
+//   tgn_mark_eval   the one slot that reads its own index back walks the node, exactly as tgn_mark<false>'s global
+//                   path does; the owners of a block's 256 slots are compacted in LDS and walked 16 lanes each.
+// A returning atomicOr on the centre word would choose the walker in one launch, but the ~1,000 candidates of a batch
+// live in ~30 bitmap words and every slot of the launch is resident at once, so their first plain reads all see the
+// bit clear: 200k returning atomics on 30 words at ~88 / us per word (MI355X_MICROARCH.md 'dequeue').  The claim
+// stores go to ~1,000 words and return nothing.
+// 2 hops: a neighbour u whose outer-centre bit a plain read finds set is being walked by the lane that set it (or
+// by u's own root walk, which covers it), so its ring row is skipped; a stale read only repeats a walk.
+__device__ __forceinline__ int64_t eval_slot_node(const Ctx& c, int q, int B, int64_t start, int Kn) {
+  if (q < B) return c.ev_src[start + q];
+  if (q < 2 * B) return c.ev_dst[start + q - B];
+  const int x = q - 2 * B;
+  return c.neg[(start + x / Kn) * Kn + x % Kn];
+}
+__global__ void __launch_bounds__(256) tgn_eval_claim(Ctx c, int* own) {
+  const int B = (int)c.ctl[TGNX_CTL_B];
+  if (B == 0 || c.ctl[TGNX_CTL_ERR] != 0) return;
+  const int64_t start = c.ctl[TGNX_CTL_BATCH_START];
+  const int gen = (int)c.ctl[TGNX_CTL_GEN];
+  const int nq = B * (2 + c.Kn);
+  // The owner of a node is its last writer, and the last writers are the slots of the workgroups that run last.  In
+  // slot order those would be the last event's negatives, which hold most of the batch's distinct candidates: ~1,000
+  // owners in the last 4 of tgn_mark_eval's 783 workgroups, 16 walks at a time (measured 40 us at 200 x 999).  So the
+  // claim deals its slots across: workgroup w of NB takes slots w, w + NB, w + 2 NB, ...: whichever workgroups run
+  // last, their slots, and so the owners, fall one to each of tgn_mark_eval's workgroups (NB >= 256 apart).  The
+  // negatives are then loaded one 64-B line per lane (a 1.6 MB table, L2-resident after the first touch).
+  const int NB = (nq + 255) / 256;
+  for (int w = blockIdx.x; w < NB; w += gridDim.x) {
+    const int q = (int)threadIdx.x * NB + w;
+    if (q >= nq) continue;
+    const int64_t v = eval_slot_node(c, q, B, start, c.Kn);
+    own[v] = q;
+    if (q < 2 * B) c.node_gen[v] = gen;
+  }
+}
+__global__ void __launch_bounds__(256) tgn_mark_eval(Ctx c, const int* own) {
+  __shared__ int64_t wv[256];
+  __shared__ int nw;
+  const int B = (int)c.ctl[TGNX_CTL_B];
+  if (B == 0 || c.ctl[TGNX_CTL_ERR] != 0) return;
+  const int64_t start = c.ctl[TGNX_CTL_BATCH_START];
+  const int nq = B * (2 + c.Kn);
+  const int tid = threadIdx.x, sl = tid & 15, grp = (tid & 63) >> 4;
+  const bool summ = !scan_direct(c.words);
+  for (int base = blockIdx.x * 256; base < nq; base += gridDim.x * 256) {  // (block-uniform)
+    if (tid == 0) nw = 0;
+    __syncthreads();
+    const int q = base + tid;
+    if (q < nq) {
+      const int64_t v = eval_slot_node(c, q, B, start, c.Kn);
+      if (own[v] == q) wv[atomicAdd(&nw, 1)] = v;
+    }
+    __syncthreads();
+    const int n = nw;
+    for (int g = tid >> 4; g < n; g += 16) {
+      // (mark_body's global path from here: loads before atomics, plain read first, no returning atomic)
+      const int64_t v = wv[g];
+      const int64_t vw = v >> 5;
+      const uint32_t vbit = 1u << (v & 31);
+      uint32_t wcv = 0u, wnv = 0u, wrv = 0u;
+      if (sl == 0) {
+        wcv = c.cb[vw];
+        wnv = c.nb[vw];
+        if (c.layers == 2) wrv = c.rb[vw];
+      }
+      int k = 0;
+      for (int j0 = 0; j0 < c.K; j0 += 16) {
+        const int j = j0 + sl, jc = min(j, c.K - 1);
+        const int64_t ej = c.eid[v * c.K + jc], u = c.nbr[v * c.K + jc];
+        const bool ok = j < c.K && ej >= 0;
+        const int64_t uw = ok ? (u >> 5) : vw;
+        const uint32_t ubit = 1u << (u & 31);
+        const uint32_t wu = c.nb[uw];
+        const uint32_t wcu = c.layers == 2 ? c.cb[uw] : 0u;
+        if (ok) {
+          if (!(wu & ubit)) atomicOr(&c.nb[uw], ubit);
+          if (summ && !wu) atomicOr(&c.nbs[uw >> 5], 1u << (uw & 31));
+          if (c.layers == 2) {
+            if (!(wcu & ubit)) atomicOr(&c.cb[uw], ubit);
+            if (summ && !wcu) atomicOr(&c.cbs[uw >> 5], 1u << (uw & 31));
+          }
+        }
+        if (ok && c.layers == 2 && !(wcu & ubit)) {
+          int ku = 0;
+          for (int i0 = 0; i0 < c.K; i0 += 8) {
+            int64_t ev[8], w[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              const int ii = min(i0 + i, c.K - 1);
+              ev[i] = c.eid[u * c.K + ii];
+              w[i] = c.nbr[u * c.K + ii];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              if (i0 + i >= c.K || ev[i] < 0) continue;
+              ++ku;
+              mark_node(c.nb, c.nbs, w[i]);
+            }
+          }
+          c.kval[u] = ku;
+        }
+        k += __popcll((__ballot(ok) >> (16 * grp)) & 0xFFFFull);
+      }
+      if (sl == 0) {
+        c.kval[v] = k;
+        if (!(wcv & vbit)) atomicOr(&c.cb[vw], vbit);
+        if (summ && !wcv) atomicOr(&c.cbs[vw >> 5], 1u << (vw & 31));
+        if (!(wnv & vbit)) atomicOr(&c.nb[vw], vbit);
+        if (summ && !wnv) atomicOr(&c.nbs[vw >> 5], 1u << (vw & 31));
+        if (c.layers == 2) {
+          if (!(wrv & vbit)) atomicOr(&c.rb[vw], vbit);
+          if (summ && !wrv) atomicOr(&c.rbs[vw >> 5], 1u << (vw & 31));
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // message-store plan of a batch: (node << 33 | dir << 32 | i), dir 0 = as source (msg_s_store),
 // 1 = as destination (msg_d_store); sorted, each (node, dir) run lists its events in batch order
 // (memory_module.py:188-191 with a stable sort): plan_part(which = 1) below.
@@ -4481,6 +4637,7 @@ struct WsLay {
   // set while the next batch's scan writes the other)
   size_t cnt2, cent2, cent_loc2, ceoff2, crank2, upd_loc2, nid2, upd2, rkeys2, rruns2, skeys2, sruns2, pcnt2;
   size_t x2r2, cent12, r_x22, ceoff12;  // (2 hops)
+  size_t own;  // [N] the deduplicated eval marking's claim word per node (tgn_eval_claim / tgn_mark_eval)
 };
 static WsLay make_ws(const tgnx_tgn_config* cfg, const Caps& k) {
   WsLay W;
@@ -4600,6 +4757,7 @@ static WsLay make_ws(const tgnx_tgn_config* cfg, const Caps& k) {
   W.cent12 = carve(off, R1 * 8);
   W.r_x22 = carve(off, R1 * 4);
   W.ceoff12 = carve(off, two ? (R1 + 1) * 4 : 0);
+  W.own = carve(off, (size_t)k.N * 4);
   W.total = off;
   return W;
 }
@@ -5607,7 +5765,16 @@ int tgnx_tgn_apply_rows_update(const tgnx_tgn_config* cfg, const tgnx_tgn_buffer
   return TGNX_OK;
 }
 
-int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t Kn, void* stream) {
+// res (tgnx_tgn_eval_step_resident): the batch from the device cursor, the deduplicated marking, and the batch's
+// reciprocal ranks copied to their event rows; everything between is tgnx_tgn_eval_step's launch sequence
+struct EvalRes {
+  int64_t lo, hi, batch;
+  int rank, world;
+  uint64_t seed;
+  double* rr_ev;
+};
+static int eval_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t Kn, void* stream,
+                          const EvalRes* res) {
   Ctx c;
   Caps k;
   WsLay W;
@@ -5616,6 +5783,16 @@ int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
   if (rc) return rc;
   TGNX_CHECK_ARG(buf->neg && buf->out_pos && buf->out_neg && buf->mrr, "tgnx_tgn_eval_step: null buffer");
   hipStream_t s = as_stream(stream);
+  if (res) {
+    TGNX_CHECK_ARG(res->rr_ev && res->batch > 0 && res->batch <= cfg->max_batch && res->world >= 1 && res->rank >= 0 &&
+                       res->rank < res->world && res->lo >= 0 && res->hi >= res->lo && res->hi <= c.nev,
+                   "tgnx_tgn_eval_step_resident: bad cursor arguments (rr_ev, batch, rank / world, or split beyond "
+                   "the event table)");
+    // buf->neg is the split's table: the kernels index it by absolute event row
+    c.neg = buf->neg - res->lo * (int64_t)Kn;
+    tgn_eval_cursor<<<1, 64, 0, s>>>(c.ctl, c.cnt, res->lo, res->hi, res->batch, res->rank, res->world, res->seed);
+    TGNX_LAUNCH_CHECK("tgn_eval_cursor");
+  }
   const float* P = c.params;
   const int D = c.D, HC = c.HC, d = c.d;
   const bool two = k.layers == 2;
@@ -5623,7 +5800,13 @@ int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
   const int Rq = two ? (int)std::min<int64_t>(c.N, (int64_t)R1q * (c.K + 1)) : R1q;  // (outer) centres
   const int Mq = (int)std::min<int64_t>(c.N, (int64_t)Rq * (c.K + 1));
   const int Eq = Rq * c.K, E1q = two ? R1q * c.K : 0;
-  {
+  if (res) {
+    int* own = reinterpret_cast<int*>(reinterpret_cast<char*>(buf->ws) + W.own);
+    const int nslot = gridn((int64_t)k.B * (2 + Kn), 256, 4096);
+    tgn_eval_claim<<<nslot, 256, 0, s>>>(c, own);
+    TGNX_LAUNCH_CHECK("tgn_eval_claim");
+    tgn_mark_eval<<<nslot, 256, 0, s>>>(c, own);
+  } else {
     const int nmark = gridn((int64_t)k.B * (2 + Kn) * 16, 256);
     tgn_mark<false><<<nmark, 256, 0, s>>>(c, nmark);
   }
@@ -5673,7 +5856,20 @@ int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
   TGNX_LAUNCH_CHECK("tgn_gru_update");
   tgn_update<<<gridn(k.Ucap, 4, 1024), 256, 0, s>>>(c, gridn(k.Ucap, 4, 1024), 0, 1, c.upd, c.cnt + CNT_U, 0, 0);
   TGNX_LAUNCH_CHECK("tgn_memory_write");
+  if (res) {
+    tgn_eval_rr<<<gridn(k.B, 256), 256, 0, s>>>(c.ctl, c.mrr, res->rr_ev, res->lo);
+    TGNX_LAUNCH_CHECK("tgn_eval_rr");
+  }
   return TGNX_OK;
+}
+int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t Kn, void* stream) {
+  return eval_step_impl(cfg, buf, Kn, stream, nullptr);
+}
+int tgnx_tgn_eval_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
+                                int64_t split_hi, int64_t batch, int32_t Kn, int32_t rank, int32_t world,
+                                uint64_t base_seed, double* rr_ev, void* stream) {
+  const EvalRes r{split_lo, split_hi, batch, rank, world, base_seed, rr_ev};
+  return eval_step_impl(cfg, buf, Kn, stream, &r);
 }
 
 size_t tgnx_tgn_flush_scratch_bytes(const tgnx_tgn_config* cfg) {

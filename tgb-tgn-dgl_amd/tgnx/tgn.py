@@ -403,6 +403,10 @@ class TgnEngine:
         # the head of step k + 1's graph; `_apply_pending` = the last step's exchange is not applied yet
         # (finish() applies it eagerly: before reading memory / parameters / the loss, and before any other call)
         self._apply_pending = False
+        # the resident eval pass (bind_eval_resident): (split_lo, split_hi, batch, Kn), and its captured graphs
+        # (single step, group size, group), held apart from the train graphs
+        self._ev = None
+        self._ev_graphs = None
         if optimizer is None:
             self.adam_m, self.adam_v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
         else:
@@ -447,6 +451,7 @@ class TgnEngine:
             self._res_buf = self._buffers(_p(self.neg_train))
             self._buf_ref = ctypes.byref(self._res_buf)
         self._graphs = None                                   # captured pointers are stale
+        self._rebind_eval()
 
     def _buffers(self, neg_ptr: int) -> TgnBuffers:
         m, ld = self.model, self.loader
@@ -557,12 +562,121 @@ class TgnEngine:
         self._keep = negs
         return self.out_pos[:B], self.out_neg[:B * Kn].view(B, Kn), self.mrr[:B]
 
+    # ------------------------------------------------------------------ resident eval pass
+    def bind_eval_resident(self, split_lo: int, split_hi: int, batch: int, negs):
+        """A validation / test pass over events [split_lo, split_hi) in batches of `batch`, resident on the device:
+        negs ([split_hi - split_lo, Kn] integers; row e - split_lo = event e's negatives) is moved to the device once
+        and kept alive here, the batch cursor lives in the control block (ctl[18], TGNX_CTL_EVAL_NB) and the
+        per-event reciprocal ranks stay in eval_rr() until eval_mrr() reads them.  Drops the eval graphs of an
+        earlier binding; the train binding and its graphs are untouched (unless Kn grows the workspace)."""
+        lo, hi, batch = int(split_lo), int(split_hi), int(batch)
+        negs = torch.as_tensor(negs)
+        if negs.dim() != 2 or negs.shape[0] != hi - lo or negs.shape[1] < 1 or negs.dtype.is_floating_point \
+                or negs.dtype == torch.bool:
+            raise ValueError(f"bind_eval_resident: negs must be an integer [split_hi - split_lo, Kn] = [{hi - lo}, Kn] "
+                             f"table, got {tuple(negs.shape)} {negs.dtype}")
+        if not (0 <= lo <= hi <= self.src.numel()) or not (0 < batch <= self.cfg.max_batch):
+            raise ValueError(f"bind_eval_resident: split [{lo}, {hi}) batch {batch} outside the event table "
+                             f"({self.src.numel()} events) / max_batch ({self.cfg.max_batch})")
+        self.finish()
+        self._prefetched = False
+        Kn = int(negs.shape[1])
+        self.ensure_neg(Kn)
+        self._ev = (lo, hi, batch, Kn)
+        self._ev_negs = negs.to(self.dev, torch.long).contiguous()
+        self._ev_rr = torch.zeros(hi - lo, dtype=torch.float64, device=self.dev)
+        self._rebind_eval()
+        self.begin_eval()
+
+    def _rebind_eval(self):
+        """The eval binding's buffer block from the engine's current tensors; its captured graphs are dropped."""
+        self._ev_graphs = None
+        if self._ev is not None:
+            self._ev_buf = self._buffers(_p(self._ev_negs))
+            self._ev_buf_ref = ctypes.byref(self._ev_buf)
+
+    def begin_eval(self):
+        """Rewind the eval cursor to split_lo (the start of a pass).  Like every non-train call it settles a deferred
+        data-parallel apply and makes the next train step prepare its batch again."""
+        self.finish()
+        self._prefetched = False
+        self.ctl[18] = 0
+
+    def _eval_step(self):
+        if self._ev is None:
+            raise RuntimeError("TgnEngine: no eval pass bound (bind_eval_resident)")
+        lo, hi, batch, Kn = self._ev
+        rc = _lib.lib().tgnx_tgn_eval_step_resident(ctypes.byref(self.cfg), self._ev_buf_ref, lo, hi, batch, Kn, self.rank,
+                                                    self.world, self.seed, ctypes.c_void_p(self._ev_rr.data_ptr()),
+                                                    self._stream())
+        if rc:
+            raise RuntimeError(f"tgnx_tgn_eval_step_resident failed: {_lib.lib().tgnx_last_error().decode()}")
+
+    def eval_resident_step(self):
+        """One eager eval batch at the cursor (a step past the end of the split is a no-op).  Returns the batch's
+        (pos, neg [max_batch, Kn], rr) buffers; the first B rows are the batch's."""
+        self.finish()
+        self._prefetched = False
+        self._eval_step()
+        Kn = self._ev[3]
+        return self.out_pos, self.out_neg[:self.cfg.max_batch * Kn].view(-1, Kn), self.mrr
+
+    def capture_eval(self, group: int = 8):
+        """One eval step as a HIP graph, and (group >= 2) `group` consecutive steps as one more, so that a pass pays
+        one graph launch per `group` batches (replay_eval_n)."""
+        self.finish()
+        torch.cuda.synchronize(self.dev)
+        saved = self.ctl.clone()
+        g1 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g1):
+            self._eval_step()
+        gk = None
+        if group >= 2:
+            gk = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gk):
+                for _ in range(group):
+                    self._eval_step()
+        torch.cuda.synchronize(self.dev)
+        self.ctl.copy_(saved)
+        self._ev_graphs = (g1, int(group) if gk is not None else 0, gk)
+
+    def replay_eval_n(self, n: int):
+        """Exactly n eval steps from the cursor: whole captured groups while at least a group's worth remains, single
+        replays for the rest."""
+        if self._ev_graphs is None:
+            raise RuntimeError("TgnEngine: no captured eval step (capture_eval after bind_eval_resident; a new binding or "
+                               "a grown workspace drops it)")
+        self.finish()
+        self._prefetched = False
+        g1, k, gk = self._ev_graphs
+        done = 0
+        while done < n:
+            if gk is not None and n - done >= k:
+                gk.replay()
+                done += k
+            else:
+                g1.replay()
+                done += 1
+
+    def eval_rr(self) -> torch.Tensor:
+        """float64 [split_hi - split_lo] on the device: event e's reciprocal rank at [e - split_lo]."""
+        return self._ev_rr
+
+    def eval_mrr(self) -> float:
+        """The reference's validation number (epoch_utils.py: the mean of the per-batch `perf` list): the mean over
+        the split's batches, the partial last one included, of each batch's mean reciprocal rank.  Formed on the
+        device by the same reductions as the per-batch loop's, so the float is the same; one synchronisation."""
+        lo, hi, batch, _ = self._ev
+        perf = [self._ev_rr[a - lo:min(hi, a + batch) - lo].mean() for a in range(lo, hi, batch)]
+        return float(torch.stack(perf).mean()) if perf else float("nan")
+
     # ------------------------------------------------------------------ resident (graph-capturable)
     def bind_resident(self, split_lo: int, split_hi: int, batch: int, dropout: bool = True):
         """Consecutive batches of `batch` events over [split_lo, split_hi), negatives drawn on the
         device; the batch cursor lives in the control block (no host arguments change per step)."""
         self.finish()
         self._group = None   # (a step group captured for a previous binding)
+        self._rebind_eval()  # (and the eval pass's graphs: held apart from the train graphs, dropped with them)
         self._res = (int(split_lo), int(split_hi), int(batch))
         self._res_drop = 1 if dropout else 0
         self._prefetched = False
