@@ -697,6 +697,55 @@ int tgnx_memstore_build_msg(const int64_t* slot, int64_t n_msg, int64_t n_s, con
                             int64_t emb_rows, const int64_t* assoc, const int64_t* stamp, const int64_t* n_id, int64_t M,
                             int32_t emb_flags, float* out, float* t_rel, void* stream);
 
+/* ---------------------------------------------------------------- test hooks
+ * The GEMM core (csrc/tgnx_gemm.h) on each tile config the library compiles, for tests/test_gpu_gemm_core.py; no
+ * product path calls these.  cfg picks the config through the alias the step itself uses (so a build-variant
+ * macro changes the probe as well). */
+enum {
+  TGNX_GEMM_PROBE_G32 = 0,  /* 16x16 wave split-K tiles, direct operands, 2 slabs per load round */
+  TGNX_GEMM_PROBE_G32L = 1, /* the same, 3 slabs per round (also the dX_enc GEMM's default) */
+  TGNX_GEMM_PROBE_GW = 2,   /* 32x32, 2x2 wave grid, register-layout split-K partials */
+  TGNX_GEMM_PROBE_G64 = 3,  /* 64x64 */
+  TGNX_GEMM_PROBE_GD = 4    /* the small-shape config of the dense fp32 GEMM entry above */
+};
+/* C[M,N] = op(A) op(B) (+ bias) (+ C if accumulate), operands as in the dense fp32 GEMM entry above.
+ * smax = 0: a direct GEMM; smax > 0: deferred split-K over at most smax splits, then the fixup launch.
+ * grid_cap > 0 caps the grid (rounded up to a multiple of 8): workgroups loop over the tiles past it.
+ * M, N, K are the capacity shape; dims_dev is NULL or three int32 on the device {Mr, Nr, Kr}, the runtime sizes
+ * (each at most its capacity; an entry < 0 means that size is not passed to the kernel).  The call reads
+ * dims_dev back (it synchronises the stream) to see which entries are passed.  Every buffer must cover the
+ * capacity shape.  a_rows (NULL or M int64 on the device, needs trans_a = 0): row m of op(A) is row a_rows[m] of
+ * A, through a two-phase gather loader; the caller keeps every entry within A's rows.
+ * ws holds the bytes the _ws_bytes call returns for (cfg, smax, M, N, K). */
+size_t tgnx_gemm_probe_ws_bytes(int32_t cfg, int32_t smax, int64_t M, int64_t N, int64_t K);
+int tgnx_gemm_probe(int32_t cfg, int32_t smax, int32_t grid_cap, int64_t M, int64_t N, int64_t K,
+                    const int32_t* dims_dev, const float* A, int64_t lda, int32_t trans_a, const int64_t* a_rows,
+                    const float* B, int64_t ldb, int32_t trans_b, float* C, int64_t ldc, const float* bias,
+                    int32_t accumulate, void* ws, size_t ws_bytes, void* stream);
+/* Several jobs in one GEMM launch and one fixup launch.  jobs[3]: jobs[0] a direct G32 GEMM, C = A B^T (smax
+ * unused); jobs[1] a deferred GW GEMM, C = A^T B; jobs[2] a deferred GW GEMM, C = A B^T (A, B row-major as stored:
+ * A is M x K, or K x M for A^T; B is N x K, or K x N for jobs[1]); each with its bias / accumulate epilogue.  The
+ * GEMM launch also hosts nb plain blocks, block b adding 1 to marks[b].  The fixup launch sums jobs[1] and jobs[2]
+ * and hosts tail_blocks extra blocks, the first `head` of them at the front of the grid (0 <= head <= tail_blocks),
+ * extra block b adding 1 to tail_marks[b].  fix_blocks (may be NULL): one int32 per output tile of jobs[1], then of
+ * jobs[2] (row-major tile order, 32x32 tiles unless the build changes GW): the block of the fixup grid that finished
+ * that tile. */
+typedef struct tgnx_gemm_probe_job {
+  int64_t M, N, K;
+  const float* A;
+  int64_t lda;
+  const float* B;
+  int64_t ldb;
+  float* C;
+  int64_t ldc;
+  const float* bias;
+  int32_t accumulate, smax;
+} tgnx_gemm_probe_job;
+size_t tgnx_gemm_probe_batch_ws_bytes(const tgnx_gemm_probe_job* jobs);
+int tgnx_gemm_probe_batch(const tgnx_gemm_probe_job* jobs, int32_t nb, int32_t* marks, int32_t head,
+                          int32_t tail_blocks, int32_t* tail_marks, int32_t* fix_blocks, void* ws, size_t ws_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,7 @@ using G32L = GemmCfg<TGNX_G32L_T, TGNX_G32L_T, TGNX_G32L_KC, TGNX_G32L_PF, TGNX_
 #endif
 using GW = GemmCfg<TGNX_GW_T, TGNX_GW_T, TGNX_GW_KC, 1, TGNX_GW_WS>;
 using G64 = GemmCfg<64, 64, 64>;   // large-M GEMMs (eval scoring)
+using GD = GemmCfg<16, 16, 64, 1, true, 3>;  // tgnx_gemm_f32's small-shape config (tgnx_gemm.hip)
 
 #ifndef TGNX_GEMM_GRID_CAP
 #define TGNX_GEMM_GRID_CAP 1024

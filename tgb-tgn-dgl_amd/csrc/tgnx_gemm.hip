@@ -7,7 +7,6 @@ using namespace tgnx;
 // TGN step's long-K config, GemmCfg::DR: this entry point is also its unit test against torch).  K up to 4
 // chunks: one workgroup per tile loops over K; larger K: split-K partials + a fixup launch.
 static bool api_big(int64_t M, int64_t N) { return ((M + 63) / 64) * ((N + 63) / 64) >= 512; }
-using GD = GemmCfg<16, 16, 64, 1, true, 3>;
 template <class CFG>
 static GemmShape gemm_api_shape(int64_t M, int64_t N, int64_t K) {
   if (K <= 4 * CFG::KC) return gemm_shape<CFG>((int)M, (int)N, (int)K);

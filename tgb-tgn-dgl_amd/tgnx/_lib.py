@@ -111,7 +111,20 @@ SIGNATURES = {
     "tgnx_tgnn_apply_pending": (ctypes.c_int, [P, P, c_vp]),
     "tgnx_tgnn_train_update": (ctypes.c_int, [P, P, c_vp]),
     "tgnx_tgnn_eval_step": (ctypes.c_int, [P, P, c_i32, c_i32, c_vp]),
+    # test hooks over the GEMM core (tgnx_gemm_probe.hip)
+    "tgnx_gemm_probe_ws_bytes": (c_sz, [c_i32, c_i32, c_i64, c_i64, c_i64]),
+    "tgnx_gemm_probe": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, P, P, c_i64, c_i32, P, P, c_i64, c_i32,
+                                       P, c_i64, P, c_i32, P, c_sz, c_vp]),
+    "tgnx_gemm_probe_batch_ws_bytes": (c_sz, [P]),
+    "tgnx_gemm_probe_batch": (ctypes.c_int, [P, c_i32, P, c_i32, c_i32, P, P, P, c_sz, c_vp]),
 }
+GEMM_PROBE_CFGS = {"G32": 0, "G32L": 1, "GW": 2, "G64": 3, "GD": 4}    # TGNX_GEMM_PROBE_* of include/tgnx.h
+
+
+class GemmProbeJob(ctypes.Structure):                                   # tgnx_gemm_probe_job
+    _fields_ = [("M", c_i64), ("N", c_i64), ("K", c_i64), ("A", P), ("lda", c_i64), ("B", P), ("ldb", c_i64),
+                ("C", P), ("ldc", c_i64), ("bias", P), ("accumulate", c_i32), ("smax", c_i32)]
+
 
 _lib = None
 
