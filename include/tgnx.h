@@ -517,6 +517,28 @@ int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
 int tgnx_tgn_eval_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                 int64_t split_hi, int64_t batch, int32_t Kn, int32_t rank, int32_t world,
                                 uint64_t base_seed, double* rr_ev, void* stream);
+/* Read-only inference: the embeddings of an explicit node list at the current stream state — out_z[i] [mem_dim] is
+ * the embedding of nodes[i] as tgnx_tgn_eval_step computes it before scoring: memory / last_update rows as stored
+ * (eval mode, memory_module.py:116-124; nothing is flushed: after train steps call tgnx_tgn_flush first), the ring
+ * sampled for the node set (twice at layers = 2), GraphAttentionEmbedding.  The launches are the eval step's up to
+ * tgn_attn_fwd (tgn_attn_fwd2), with the roots taken from `nodes` (tgn_embed_claim / tgn_embed_mark), the scan's
+ * node-set walk alone (no batch, so no insert / store plans), and one gather of the roots' rows into out_z; no
+ * scoring, no update_state, no ring insert.  Duplicates are allowed.  A node outside [0, num_nodes) is never used as
+ * an index: its row is zero-filled and it is counted into *n_invalid (a device int64 the caller zeroes; may be NULL).
+ * n <= tgnx_tgn_embed_max_nodes(cfg) = the eval root capacity min(num_nodes, max_batch * (2 + max_neg)); more is
+ * TGNX_EINVAL (the caller chunks: calls are independent).  n = 0 does nothing.
+ * Read-only: memory, last_update, the message stores, the ring, node_gen, parameters, gradients and Adam moments are
+ * untouched, and so is every ctl word but two — TGNX_CTL_GEN advances by one per call (node_gen stamps are compared
+ * to it: it stays monotonic, and no stamp equals the new value, so the update list is empty) and TGNX_CTL_ERR takes
+ * the capacity-overflow bit the scan would set.  The kernels read the batch geometry from a private copy of ctl in
+ * the workspace (B = n, GEN = the new value; the scan's SUM_E / SUM_S additions land there); on a nonzero ERR the
+ * call computes nothing and zero-fills out_z.  assoc and the workspace (sampled sets, bitmaps, the scan-output set 0)
+ * are scratch as for every step: a pipelined / parity-set train step after it must run with prefetched = 0. */
+int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg);
+int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                   float* out_z /* [n, mem_dim] */, int64_t* n_invalid /* device, caller-zeroed, may be NULL */,
+                   void* stream);
+
 /* train(False): update the memory of every node from its stored messages, clear the stores
  * (memory_module.py:209-215).  Every row is computed from the pre-flush state (:212 updates arange(N) at
  * once).  Graphs with more nodes than the workspace's GRU row capacity run in chunks that read a snapshot
@@ -561,6 +583,27 @@ int tgnx_link_predictor(int64_t n_src, int64_t M, int64_t d_in, int64_t D, const
                         const float* w_src, const float* b_src, const float* w_dst, const float* b_dst,
                         const float* w_out, const float* b_out, int32_t sigmoid, float* out, void* ws,
                         size_t ws_bytes, void* stream);
+
+/* LinkPredictor over ALL pairs with the selection fused in (csrc/tgnx_topk.hip): for every source row q the k
+ * candidates with the largest logit[q][c] = w_out · relu(W_src z_src[q] + b_src + W_dst z_cand[c] + b_dst) + b_out,
+ * without a [n_src * n_cand, d_in] operand (the tiled tgnx_link_predictor needs one).  z_src [n_src, d_in], z_cand
+ * [n_cand, d_in]; weights as tgnx_link_predictor (b_src / b_dst may be NULL); 1 <= k <= TGNX_TOPK_MAX, D <= 256.
+ * The selection is on the LOGIT (fp32 sigmoid is exactly 1.0 above ~17: ties at the top of a trained ranking) under
+ * one total order: larger logit first, equal logits by lower candidate position, so the result does not depend on
+ * how the work is split; a NaN logit is never selected.  out_idx [n_src, k]: positions into z_cand; out_val
+ * [n_src, k]: the selected logits, or their sigmoid when sigmoid = 1.  Slots past n_cand (k > n_cand): idx -1, val
+ * -INFINITY (0 with sigmoid = 1).  out_all (optional, [n_src, n_cand]): every logit exactly as the selection
+ * compared it (logits, whatever `sigmoid`), written by the same pass.  n_src = 0 does nothing; n_cand = 0 fills the
+ * padding.  No float atomics, no allocation, no host synchronisation: graph-capturable and run-to-run identical.
+ * ws: tgnx_link_predictor_topk_ws_bytes bytes (Hs, Hd, the per-chunk partial lists; monotone in n_cand). */
+#define TGNX_TOPK_MAX 128
+size_t tgnx_link_predictor_topk_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k);
+int tgnx_link_predictor_topk(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                             const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                             const float* b_dst, const float* w_out, const float* b_out, int32_t k, int32_t sigmoid,
+                             float* out_val /* [n_src, k] */, int64_t* out_idx /* [n_src, k] */,
+                             float* out_all /* optional [n_src, n_cand], may be NULL */, void* ws, size_t ws_bytes,
+                             void* stream);
 
 /* TransformerConv's attention (modules/emb_module.py:21-29; PyG TransformerConv, concat, no beta): for
  * destination i with incoming edges p in [indptr[i], indptr[i+1]) (rows of the per-edge k, v, e [E, H*C];

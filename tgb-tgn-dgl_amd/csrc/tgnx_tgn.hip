@@ -706,6 +706,117 @@ __global__ void __launch_bounds__(256) tgn_mark_eval(Ctx c, const int* own) {
   }
 }
 
+// ------------------------------------------------------------------ read-only embeddings (tgnx_tgn_embed)
+// The eval forward for an explicit node list.  The launches after these read the batch geometry from c.ctl, which
+// tgnx_tgn_embed points at a private copy of the control block in the workspace (as the fixup's view reads a
+// snapshot): B = n makes them run, GEN = the advanced value keeps the update list empty (no node_gen stamp equals
+// it), and the scan's SUM_E / SUM_S additions land in the copy.  Of the live block only GEN (tgn_embed_claim) and
+// ERR (tgn_embed_gather) are written.
+//   tgn_embed_claim   tgn_eval_claim over nodes[]: slot i stores i into own[nodes[i]] (the last writer owns the node);
+//                     ids outside [0, N) are counted and skipped; nothing is stamped in node_gen.  Block 0 thread 0
+//                     writes the private ctl (no other thread of this launch reads it).
+//   tgn_embed_mark    tgn_mark_eval over nodes[]: the owner slot walks the node's ring row.
+//   tgn_embed_gather  out_z[i] = the root row of nodes[i] (zeros for an invalid id, or when ERR is set).
+__global__ void __launch_bounds__(256) tgn_embed_claim(Ctx c, int64_t* live_ctl, int* own, const int64_t* nodes, int n,
+                                                       int64_t* n_invalid) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t gen = live_ctl[TGNX_CTL_GEN] + 1;
+    live_ctl[TGNX_CTL_GEN] = gen;
+    for (int i = 0; i < TGNX_CTL_WORDS; ++i) c.ctl[i] = live_ctl[i];
+    c.ctl[TGNX_CTL_B] = n;
+    c.ctl[TGNX_CTL_BATCH_START] = 0;
+  }
+  int bad = 0;
+  for (int q = blockIdx.x * 256 + threadIdx.x; q < n; q += gridDim.x * 256) {
+    const int64_t v = nodes[q];
+    if (v < 0 || v >= c.N) ++bad;
+    else own[v] = q;
+  }
+  if (bad && n_invalid) atomicAdd(reinterpret_cast<unsigned long long*>(n_invalid), (unsigned long long)bad);
+}
+// one owner's walk of node v by 16 lanes (sl: lane of the 16, grp: which 16 of the wave) — tgn_mark_eval's walk
+// restated for the node-list kernel (that kernel is left as measured: folding both onto one function changed its
+// register allocation): loads before atomics, plain read first, no returning atomic
+__device__ __forceinline__ void embed_walk(const Ctx& c, int64_t v, int sl, int grp, bool summ) {
+  const int64_t vw = v >> 5;
+  const uint32_t vbit = 1u << (v & 31);
+  uint32_t wcv = 0u, wnv = 0u, wrv = 0u;
+  if (sl == 0) {
+    wcv = c.cb[vw];
+    wnv = c.nb[vw];
+    if (c.layers == 2) wrv = c.rb[vw];
+  }
+  int k = 0;
+  for (int j0 = 0; j0 < c.K; j0 += 16) {
+    const int j = j0 + sl, jc = min(j, c.K - 1);
+    const int64_t ej = c.eid[v * c.K + jc], u = c.nbr[v * c.K + jc];
+    const bool ok = j < c.K && ej >= 0;
+    const int64_t uw = ok ? (u >> 5) : vw;
+    const uint32_t ubit = 1u << (u & 31);
+    const uint32_t wu = c.nb[uw];
+    const uint32_t wcu = c.layers == 2 ? c.cb[uw] : 0u;
+    if (ok) {
+      if (!(wu & ubit)) atomicOr(&c.nb[uw], ubit);
+      if (summ && !wu) atomicOr(&c.nbs[uw >> 5], 1u << (uw & 31));
+      if (c.layers == 2) {
+        if (!(wcu & ubit)) atomicOr(&c.cb[uw], ubit);
+        if (summ && !wcu) atomicOr(&c.cbs[uw >> 5], 1u << (uw & 31));
+      }
+    }
+    if (ok && c.layers == 2 && !(wcu & ubit)) {
+      int ku = 0;
+      for (int i0 = 0; i0 < c.K; i0 += 8) {
+        int64_t ev[8], w[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int ii = min(i0 + i, c.K - 1);
+          ev[i] = c.eid[u * c.K + ii];
+          w[i] = c.nbr[u * c.K + ii];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if (i0 + i >= c.K || ev[i] < 0) continue;
+          ++ku;
+          mark_node(c.nb, c.nbs, w[i]);
+        }
+      }
+      c.kval[u] = ku;
+    }
+    k += __popcll((__ballot(ok) >> (16 * grp)) & 0xFFFFull);
+  }
+  if (sl == 0) {
+    c.kval[v] = k;
+    if (!(wcv & vbit)) atomicOr(&c.cb[vw], vbit);
+    if (summ && !wcv) atomicOr(&c.cbs[vw >> 5], 1u << (vw & 31));
+    if (!(wnv & vbit)) atomicOr(&c.nb[vw], vbit);
+    if (summ && !wnv) atomicOr(&c.nbs[vw >> 5], 1u << (vw & 31));
+    if (c.layers == 2) {
+      if (!(wrv & vbit)) atomicOr(&c.rb[vw], vbit);
+      if (summ && !wrv) atomicOr(&c.rbs[vw >> 5], 1u << (vw & 31));
+    }
+  }
+}
+__global__ void __launch_bounds__(256) tgn_embed_mark(Ctx c, const int* own, const int64_t* nodes, int n) {
+  __shared__ int64_t wv[256];
+  __shared__ int nw;
+  if (c.ctl[TGNX_CTL_ERR] != 0) return;
+  const int tid = threadIdx.x, sl = tid & 15, grp = (tid & 63) >> 4;
+  const bool summ = !scan_direct(c.words);
+  for (int base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {  // (block-uniform)
+    if (tid == 0) nw = 0;
+    __syncthreads();
+    const int q = base + tid;
+    if (q < n) {
+      const int64_t v = nodes[q];
+      if (v >= 0 && v < c.N && own[v] == q) wv[atomicAdd(&nw, 1)] = v;
+    }
+    __syncthreads();
+    const int nown = nw;
+    for (int g = tid >> 4; g < nown; g += 16) embed_walk(c, wv[g], sl, grp, summ);
+    __syncthreads();
+  }
+}
+
 // message-store plan of a batch: (node << 33 | dir << 32 | i), dir 0 = as source (msg_s_store),
 // 1 = as destination (msg_d_store); sorted, each (node, dir) run lists its events in batch order
 // (memory_module.py:188-191 with a stable sort): plan_part(which = 1) below.
@@ -4554,6 +4665,19 @@ __global__ void __launch_bounds__(256) tgn_score(Ctx c) {
   if (tid == 0) c.mrr[i] = 1.0 / (0.5 * ((double)cnt2[0] + (double)cnt2[1]) + 1.0);
 }
 
+// tgnx_tgn_embed's last launch (c: the root level's view, c.ctl the private copy): a wave per output row
+__global__ void __launch_bounds__(256) tgn_embed_gather(Ctx c, int64_t* live_ctl, const int64_t* nodes, int n, float* out_z) {
+  const int64_t err = c.ctl[TGNX_CTL_ERR];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && err != live_ctl[TGNX_CTL_ERR]) live_ctl[TGNX_CTL_ERR] |= err;
+  const int lane = threadIdx.x & 63, D = c.D;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const int64_t v = nodes[i];
+    const bool ok = err == 0 && v >= 0 && v < c.N;
+    const float* z = ok ? c.Zc + (int64_t)root_row(c, v) * c.HC : nullptr;
+    for (int k = lane; k < D; k += WAVE) out_z[(int64_t)i * D + k] = ok ? z[k] : 0.f;
+  }
+}
+
 static size_t carve(size_t& off, size_t bytes) {
   size_t o = off;
   off += (bytes + 255) & ~size_t(255);
@@ -4638,6 +4762,7 @@ struct WsLay {
   size_t cnt2, cent2, cent_loc2, ceoff2, crank2, upd_loc2, nid2, upd2, rkeys2, rruns2, skeys2, sruns2, pcnt2;
   size_t x2r2, cent12, r_x22, ceoff12;  // (2 hops)
   size_t own;  // [N] the deduplicated eval marking's claim word per node (tgn_eval_claim / tgn_mark_eval)
+  size_t qctl;  // [TGNX_CTL_WORDS] tgnx_tgn_embed's private copy of the control block
 };
 static WsLay make_ws(const tgnx_tgn_config* cfg, const Caps& k) {
   WsLay W;
@@ -4758,6 +4883,7 @@ static WsLay make_ws(const tgnx_tgn_config* cfg, const Caps& k) {
   W.r_x22 = carve(off, R1 * 4);
   W.ceoff12 = carve(off, two ? (R1 + 1) * 4 : 0);
   W.own = carve(off, (size_t)k.N * 4);
+  W.qctl = carve(off, (size_t)TGNX_CTL_WORDS * 8);
   W.total = off;
   return W;
 }
@@ -5870,6 +5996,76 @@ int tgnx_tgn_eval_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffe
                                 uint64_t base_seed, double* rr_ev, void* stream) {
   const EvalRes r{split_lo, split_hi, batch, rank, world, base_seed, rr_ev};
   return eval_step_impl(cfg, buf, Kn, stream, &r);
+}
+
+// eval_step_impl's launches up to the embedding, for the roots nodes[n]; see tgn_embed_claim
+int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg) {
+  if (check_cfg(cfg)) return 0;
+  return make_caps(cfg).R1cap;
+}
+int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                   float* out_z, int64_t* n_invalid, void* stream) {
+  Ctx c;
+  Caps k;
+  WsLay W;
+  TGNX_CHECK_ARG(cfg && buf, "tgnx_tgn_embed: null config or buffers");
+  int rc = make_ctx(cfg, buf, cfg->max_neg < 1 ? 1 : cfg->max_neg, c, k, W);
+  if (rc) return rc;
+  TGNX_CHECK_ARG(n >= 0 && n <= k.R1cap, "tgnx_tgn_embed: n = %lld beyond tgnx_tgn_embed_max_nodes = %d", (long long)n,
+                 k.R1cap);
+  if (n == 0) return TGNX_OK;
+  TGNX_CHECK_ARG(nodes && out_z, "tgnx_tgn_embed: null pointer");
+  hipStream_t s = as_stream(stream);
+  char* ws = reinterpret_cast<char*>(buf->ws);
+  int* own = reinterpret_cast<int*>(ws + W.own);
+  int64_t* live = c.ctl;
+  c.ctl = reinterpret_cast<int64_t*>(ws + W.qctl);
+  c.errw = c.ctl + TGNX_CTL_ERR;
+  const float* P = c.params;
+  const int D = c.D, HC = c.HC, d = c.d, nn = (int)n;
+  const bool two = k.layers == 2;
+  const int R1q = k.R1cap;                                                               // roots
+  const int Rq = two ? (int)std::min<int64_t>(c.N, (int64_t)R1q * (c.K + 1)) : R1q;  // (outer) centres
+  const int Mq = (int)std::min<int64_t>(c.N, (int64_t)Rq * (c.K + 1));
+  const int Eq = Rq * c.K, E1q = two ? R1q * c.K : 0;
+  const int nslot = gridn(n, 256, 4096);
+  tgn_embed_claim<<<nslot, 256, 0, s>>>(c, live, own, nodes, nn, n_invalid);
+  TGNX_LAUNCH_CHECK("tgn_embed_claim");
+  tgn_embed_mark<<<nslot, 256, 0, s>>>(c, own, nodes, nn);
+  TGNX_LAUNCH_CHECK("tgn_embed_mark");
+  // role 0 alone: roles >= 1 build the insert / store plans of a batch's events, and there is no batch
+  tgn_scan<false><<<1, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
+  TGNX_LAUNCH_CHECK("tgn_scan");
+  const int nedge = gridn((int64_t)Rq * c.K, 4, 4096);
+  tgn_agg_emit<-1><<<nedge + gridn(Mq, 256), 256, 0, s>>>(c, 1, nedge, nullptr, nullptr, 0, 0);
+  TGNX_LAUNCH_CHECK("tgn_emit");
+  const LoadEdgeAttr ea{c.encE, c.e_id, c.ev_msg, D, d};
+  const auto j_edge = gemm_job<G32>(gemm_shape<G32>(Eq, HC, D + d, c.cnt + CNT_E), ea,
+                                    LoadRowK{P + c.L.we, HC, D + d, D + d}, EpiStore{c.Ep, nullptr, HC, 0}, (float*)nullptr);
+  const auto j_proj = gemm_job<G32>(gemm_shape<G32>(Mq, 4 * HC, D, c.cnt + CNT_M), LoadZ{c.Z0, c.mem, c.nid, D, 1},
+                                    LoadProjW{P + c.L.wq, c.L.pw, HC, D}, EpiProj{P + c.L.bq, c.L.pb, c.P, HC},
+                                    (float*)nullptr);
+  if (two)
+    gemmN_launch(s, j_edge, j_proj,
+                 gemm_job<G32>(gemm_shape<G32>(E1q, HC, D + d, c.cnt + CNT_E1),
+                               LoadEdgeAttrMap{c.encE, c.e1_id, c.e1_e2, c.ev_msg, D, d},
+                               LoadRowK{P + c.L.we2, HC, D + d, D + d}, EpiStore{c.Ep2, nullptr, HC, 0}, (float*)nullptr));
+  else
+    gemmN_launch(s, j_edge, j_proj);
+  TGNX_LAUNCH_CHECK("tgn_edge_proj");
+  tgn_attn_fwd<false><<<gridn(Rq, 4, 1 << 20), 256, 0, s>>>(c);
+  TGNX_LAUNCH_CHECK("tgn_attn_fwd");
+  const Ctx cr = two ? root_view(c) : c;
+  if (two) {
+    gemm_launch<G32>(gemm_shape<G32>(Rq, 4 * HC, HC, c.cnt + CNT_R), LoadRowK{c.Zc, Rq, HC, HC},
+                     LoadProjW{P + c.L.wq2, c.L.pw, HC, HC}, EpiProj{P + c.L.bq2, c.L.pb, c.P2, HC}, nullptr, s);
+    TGNX_LAUNCH_CHECK("tgn_proj2");
+    tgn_attn_fwd<false><<<gridn(R1q, 4, 1 << 20), 256, 0, s>>>(cr);
+    TGNX_LAUNCH_CHECK("tgn_attn_fwd2");
+  }
+  tgn_embed_gather<<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
+  TGNX_LAUNCH_CHECK("tgn_embed_gather");
+  return TGNX_OK;
 }
 
 size_t tgnx_tgn_flush_scratch_bytes(const tgnx_tgn_config* cfg) {

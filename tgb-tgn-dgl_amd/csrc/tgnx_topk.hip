@@ -1,0 +1,348 @@
+// Fused all-pairs LinkPredictor scoring + top-k selection (tgnx_link_predictor_topk; torch.ops.tgnx.predictor_topk):
+// for every source row q the k candidates c with the largest
+//   logit[q][c] = w_out · relu(W_src z_src[q] + b_src + W_dst z_cand[c] + b_dst) + b_out      (decoder.py:12-27)
+// without the [n_src · n_cand, D] operand the tiled predictor op needs.
+//
+//   Hs = z_src W_src^T + b_src [n_src, ldh], Hd = z_cand W_dst^T + b_dst [n_cand, ldh] on the MFMA GEMM (ldh = D
+//   rounded up to 4 floats: every row starts 16-B aligned);
+//   topk_pairs   one workgroup per (tile of 16 sources, chunk of 256 / 512 candidates): the pair logits, then the
+//                chunk's k best per source as a partial list;
+//   topk_merge   one wave per source: the k best of its chunks' lists (staged in LDS).
+//
+// The pair work is n_src · n_cand · D relu-FMAs (add, max, fma per term; the ReLU sits inside the contraction, so no
+// MFMA).  A thread owns one candidate: its Hd row streams through registers 16 B at a time and every element is used
+// for the tile's 16 sources, whose Hs rows sit in LDS k-major ([k][16]: four ds_read_b128 per k, every lane the same
+// address, a broadcast), so one LDS instruction feeds 12 vector instructions.  Each logit is one sequential fma chain
+// over k = 0 .. D - 1: its value does not depend on the grid, the chunk size or the tile a source falls in.
+//
+// Selection is on the logits under one total order — larger logit first, equal logits (float ==, so -0 = +0) by lower
+// candidate position; NaN logits are never selected.  The chunk's logits stay in LDS ([16][chunk]); a wave takes four
+// sources and picks k times the best entry strictly after its previous pick in that order (a strided scan, a DPP max
+// of the values, a DPP min of the positions attaining it): no marking, no sort.  Measured at 200 x 9,227 x 100: the
+// pair work ~26 us, a select round ~1.7 us, i.e. 36 % of the kernel at k = 10 and the larger part from k ~ 16 (the
+// select is linear in k; k <= TGNX_TOPK_MAX; a sort per chunk would win at large k and is not built).  The global top-k
+// is a subset of the chunks' top-k lists, so the merge (same order, positions global) is exact.
+// Chunks rather than one workgroup per source tile walking every candidate: 200 sources are 13 tiles, 13 workgroups
+// on 256 CUs; chunked, the wiki shape (200 x 9,227) is 13 x 37 workgroups.  Partials cost n_src · chunks · k · 8 B.
+// No atomics, no allocation, no host synchronisation: graph-capturable, run-to-run identical.
+#include <limits.h>
+#include <math.h>
+
+#include <algorithm>
+
+#include "tgnx_common.h"
+
+using namespace tgnx;
+
+namespace {
+
+constexpr int TK_BLOCK = 256;
+constexpr int TK_TQ = 16;        // sources per workgroup (four per wave in the select)
+constexpr int TK_CHUNK_MIN = 256, TK_CHUNK_MAX = 512;  // candidates per workgroup (LDS: 16 x chunk logits, <= 32 KB)
+constexpr int64_t TK_DMAX = 256;
+constexpr int TK_G = 4;          // 16-B vectors of a candidate's Hd row per load group (two groups in registers)
+constexpr int TK_MTILE = 896;    // partial entries per merge pass (+ the running list: 1024 entries, 8 KB per wave)
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+int64_t ld_of(int64_t D) { return (D + 3) & ~int64_t(3); }
+// 512 candidates per workgroup (half the select rounds per candidate) once that still gives every CU a workgroup
+int chunk_of(int64_t n_src, int64_t n_cand) {
+  return ceil_div(n_src, TK_TQ) * ceil_div(n_cand, TK_CHUNK_MAX) >= 256 ? TK_CHUNK_MAX : TK_CHUNK_MIN;
+}
+size_t pairs_smem(int64_t ldh, int chunk) { return (size_t)(ldh * TK_TQ + ldh + (int64_t)TK_TQ * chunk) * sizeof(float); }
+
+struct TopkWs {
+  float *hs, *hd, *pval;
+  int* pidx;
+  char* gemm;
+  size_t used;
+};
+// the partial lists are sized for the smaller chunk (the larger count), so the size is monotone in n_cand
+TopkWs topk_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D, int32_t k) {
+  const int64_t ldh = ld_of(D), ncmax = ceil_div(n_cand, TK_CHUNK_MIN);
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = 0;
+  TopkWs w;
+  w.hs = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_src * ldh * 4);
+  w.hd = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_cand * ldh * 4);
+  w.pval = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_src * ncmax * k * 4);
+  w.pidx = reinterpret_cast<int*>(p + off);
+  off += align256((size_t)n_src * ncmax * k * 4);
+  w.gemm = p + off;
+  w.used = off;
+  return w;
+}
+
+// the pick after (pv, pj) in the order among a lane's entries (v, j): larger v, then smaller j
+__device__ __forceinline__ bool after(float v, int j, float pv, int pj) { return v < pv || (v == pv && j > pj); }
+// the wave's best (value, position) from every lane's best (position INT_MAX: none); every lane gets it
+__device__ __forceinline__ void wave_best(float& bv, int& bj) {
+  const float m = wave_max_f(bv);
+  bj = wave_min_i(bv == m ? bj : INT_MAX);
+  bv = m;
+}
+
+__global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_cand, int D, int ldh, int chunk, int nc,
+                                                       const float* __restrict__ hs, const float* __restrict__ hd,
+                                                       const float* __restrict__ w_out, const float* __restrict__ b_out,
+                                                       int k, float* __restrict__ pval, int* __restrict__ pidx,
+                                                       float* __restrict__ out_all) {
+  extern __shared__ __attribute__((aligned(16))) float tk_smem[];
+  float* hsT = tk_smem;                     // [ldh][16] the tile's Hs rows, k-major; rows past n_src and columns past D zero
+  float* wl = hsT + (size_t)ldh * TK_TQ;    // [ldh] w_out, zero past D
+  float* L = wl + ldh;                      // [16][chunk] the chunk's logits
+  const int tid = threadIdx.x;
+  const int64_t tile = blockIdx.x / nc, q0 = tile * TK_TQ;
+  const int64_t cbase = (int64_t)(blockIdx.x % nc) * chunk;
+  const int nq = (int)min((int64_t)TK_TQ, n_src - q0);
+  const int nvalid = (int)min((int64_t)chunk, n_cand - cbase);
+  for (int x = tid; x < ldh * TK_TQ; x += TK_BLOCK) {
+    const int kk = x / TK_TQ, q = x % TK_TQ;
+    hsT[x] = (q < nq && kk < D) ? hs[(q0 + q) * ldh + kk] : 0.f;
+  }
+  for (int x = tid; x < ldh; x += TK_BLOCK) wl[x] = x < D ? w_out[x] : 0.f;
+  __syncthreads();
+  const float bo = b_out[0];
+  for (int c0 = 0; c0 < chunk; c0 += TK_BLOCK) {  // (block-uniform)
+    const int cl = c0 + tid;
+    const bool valid = cl < nvalid;
+    // a thread past the chunk's end reads the last valid row (in bounds, result discarded)
+    const float4* row = reinterpret_cast<const float4*>(hd + (cbase + min(cl, nvalid - 1)) * ldh);
+    float acc[TK_TQ];
+#pragma unroll
+    for (int i = 0; i < TK_TQ; ++i) acc[i] = 0.f;
+    // the row in groups of TK_G 16-B vectors, the next group's loads in flight while this one is used (a load per
+    // iteration and its use right behind it left the L2 latency exposed 25 times per row at D = 100).  Past the
+    // row's end the last vector is loaded again and not used.
+    const int nv = ldh >> 2;
+    float4 nxt[TK_G];
+#pragma unroll
+    for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
+    for (int v0 = 0; v0 < nv; v0 += TK_G) {
+      float4 cur[TK_G];
+#pragma unroll
+      for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
+#pragma unroll
+      for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
+#pragma unroll
+      for (int u = 0; u < TK_G; ++u) {
+        if (v0 + u >= nv) break;  // (uniform)
+        const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int kk = (v0 + u) * 4 + e;
+          const float hv = kk < D ? he[e] : 0.f;  // (the row's pad columns are not written by the GEMM)
+          const float wk = wl[kk];
+          const float4* hq = reinterpret_cast<const float4*>(hsT + kk * TK_TQ);
+#pragma unroll
+          for (int g = 0; g < TK_TQ / 4; ++g) {
+            const float4 s = hq[g];
+            acc[4 * g + 0] = fmaf(wk, fmaxf(s.x + hv, 0.f), acc[4 * g + 0]);
+            acc[4 * g + 1] = fmaf(wk, fmaxf(s.y + hv, 0.f), acc[4 * g + 1]);
+            acc[4 * g + 2] = fmaf(wk, fmaxf(s.z + hv, 0.f), acc[4 * g + 2]);
+            acc[4 * g + 3] = fmaf(wk, fmaxf(s.w + hv, 0.f), acc[4 * g + 3]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < TK_TQ; ++i) {
+      const float lg = acc[i] + bo;
+      L[i * chunk + cl] = lg;  // (entries past nvalid are never scanned)
+      if (out_all && valid && i < nq) out_all[(q0 + i) * n_cand + cbase + cl] = lg;
+    }
+  }
+  __syncthreads();
+  // the chunk's k best per source: wave w takes sources 4 w .. 4 w + 3, their four selections side by side (four
+  // independent scan / reduce chains per round; rows past nq hold the zero source's logits and are not stored)
+  constexpr int QW = TK_TQ / (TK_BLOCK / WAVE);
+  const int lane = tid & 63, i0 = (tid >> 6) * QW;
+  const int64_t cj = blockIdx.x % nc;
+  float pv[QW];
+  int pj[QW];
+#pragma unroll
+  for (int u = 0; u < QW; ++u) {
+    pv[u] = INFINITY;
+    pj[u] = -1;
+  }
+  for (int r = 0; r < k; ++r) {
+    float bv[QW];
+    int bj[QW];
+#pragma unroll
+    for (int u = 0; u < QW; ++u) {
+      bv[u] = -INFINITY;
+      bj[u] = INT_MAX;
+    }
+    for (int j = lane; j < nvalid; j += WAVE) {  // j ascends: the first of a lane's equal values stays
+#pragma unroll
+      for (int u = 0; u < QW; ++u) {
+        const float v = L[(i0 + u) * chunk + j];
+        if (after(v, j, pv[u], pj[u]) && (v > bv[u] || bj[u] == INT_MAX)) {
+          bv[u] = v;
+          bj[u] = j;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < QW; ++u) {
+      wave_best(bv[u], bj[u]);
+      if (lane == 0 && i0 + u < nq) {  // (none left, position INT_MAX: padding)
+        pval[((q0 + i0 + u) * nc + cj) * k + r] = bj[u] == INT_MAX ? -INFINITY : L[(i0 + u) * chunk + bj[u]];
+        pidx[((q0 + i0 + u) * nc + cj) * k + r] = bj[u] == INT_MAX ? -1 : (int)(cbase + bj[u]);
+      }
+      pv[u] = bv[u];
+      pj[u] = bj[u];
+    }
+  }
+}
+
+// Wave per source: the k best of its nc chunk lists (k entries each, sorted in the order, position -1: the padding
+// at the tail of a short chunk's list), then padding.  A k-way merge by list heads: the lists are staged in LDS,
+// TK_MTILE / k of them per pass beside the running list of the picks so far (itself sorted; one pass at the wiki
+// shape: 37 lists of 10), a lane looks at the heads of its lists, the wave picks the best head and its lane advances
+// that list.  A round costs lists / 64 head reads and one reduction whatever k is.  (Rescanning every staged entry
+// per round was k times that: 1.2 ms at k = 128 over 37 chunks; scanning the lists in global memory paid a dependent
+// L2 round trip per round.)
+__global__ void __launch_bounds__(TK_BLOCK) topk_merge(int64_t n_src, int nc, int k, const float* __restrict__ pval,
+                                                       const int* __restrict__ pidx, int sigmoid,
+                                                       float* __restrict__ out_val, int64_t* __restrict__ out_idx) {
+  constexpr int WPB = TK_BLOCK / WAVE, CAP = TGNX_TOPK_MAX + TK_MTILE;
+  __shared__ float sv[WPB][CAP];
+  __shared__ int si[WPB][CAP];
+  __shared__ int sh[WPB][TK_MTILE + 1];  // list heads: [0] the running list, [1 + l] the pass's list l
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t q = blockIdx.x * (int64_t)WPB + wv;
+  const bool live = q < n_src;  // (wave-uniform; a dead wave keeps the block's barriers)
+  const float* v0 = pval + (live ? q : 0) * (int64_t)nc * k;
+  const int* j0 = pidx + (live ? q : 0) * (int64_t)nc * k;
+  float* V = sv[wv];
+  int* I = si[wv];
+  int* H = sh[wv];
+  for (int x = lane; x < TGNX_TOPK_MAX; x += WAVE) I[x] = -1;  // the running list: empty
+  float kv[2] = {-INFINITY, -INFINITY};  // this lane's picks r = lane, lane + 64 of the latest pass
+  int kj[2] = {INT_MAX, INT_MAX};
+  const int lpt = TK_MTILE / k;  // lists per pass (>= 7)
+  for (int c0 = 0; c0 == 0 || c0 < nc; c0 += lpt) {  // (block-uniform; nc = 0: one pass over nothing)
+    const int nl = max(0, min(lpt, nc - c0)), nt = nl * k;
+    const int64_t t0 = (int64_t)c0 * k;
+    for (int x0 = lane; x0 < nt; x0 += 4 * WAVE) {  // four entries per lane in flight
+      float tv[4];
+      int tj[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int x = x0 + u * WAVE;
+        const bool ok = live && x < nt;
+        tv[u] = ok ? v0[t0 + x] : 0.f;
+        tj[u] = ok ? j0[t0 + x] : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int x = x0 + u * WAVE;
+        if (x < nt) {
+          V[TGNX_TOPK_MAX + x] = tv[u];
+          I[TGNX_TOPK_MAX + x] = tj[u];
+        }
+      }
+    }
+    for (int l = lane; l <= nl; l += WAVE) H[l] = 0;
+    __syncthreads();
+    for (int r = 0; r < k; ++r) {
+      float bv = -INFINITY;
+      int bj = INT_MAX, bl = 0;
+      for (int l = lane; l <= nl; l += WAVE) {
+        const int h = H[l];
+        const int e = l == 0 ? min(h, TGNX_TOPK_MAX - 1) : TGNX_TOPK_MAX + (l - 1) * k + min(h, k - 1);
+        const int j = h < k ? I[e] : -1;
+        const float v = V[e];
+        if (j >= 0 && (bj == INT_MAX || v > bv || (v == bv && j < bj))) {
+          bv = v;
+          bj = j;
+          bl = l;
+        }
+      }
+      const float bx = bv;  // the entry's own value (-0 / +0 compare equal: the reduced max may be the other)
+      const int mine = bj;
+      wave_best(bv, bj);
+      const unsigned long long who = __ballot(mine == bj && bj != INT_MAX);  // (positions are distinct: one lane)
+      const int wl = who ? __ffsll((long long)who) - 1 : 0;
+      const float val = who ? lane_f(bx, wl) : -INFINITY;
+      if (who && lane == wl) H[bl] += 1;
+      if (lane == (r & 63)) {
+        kv[r >> 6] = val;
+        kj[r >> 6] = bj;
+      }
+    }
+    __syncthreads();  // every read of this pass is done: the picks (sorted) become the running list
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      if (lane + 64 * h < k) {
+        V[lane + 64 * h] = kv[h];
+        I[lane + 64 * h] = kj[h] == INT_MAX ? -1 : kj[h];
+      }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int r = lane + 64 * h;
+    if (!live || r >= k) continue;
+    const bool none = kj[h] == INT_MAX;
+    out_val[q * k + r] = none ? (sigmoid ? 0.f : -INFINITY) : (sigmoid ? 1.f / (1.f + expf(-kv[h])) : kv[h]);
+    out_idx[q * k + r] = none ? -1 : kj[h];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tgnx_link_predictor_topk_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k) {
+  if (n_src < 0 || n_cand < 0 || d_in <= 0 || D <= 0 || D > TK_DMAX || k < 1 || k > TGNX_TOPK_MAX) return 256;
+  const TopkWs w = topk_ws(nullptr, n_src, n_cand, D, k);
+  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
+                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
+  return w.used + align256(g) + 256;
+}
+
+int tgnx_link_predictor_topk(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                             const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                             const float* b_dst, const float* w_out, const float* b_out, int32_t k, int32_t sigmoid,
+                             float* out_val, int64_t* out_idx, float* out_all, void* ws, size_t ws_bytes,
+                             void* stream) {
+  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "tgnx_link_predictor_topk: k must be in [1, %d], got %d", TGNX_TOPK_MAX, k);
+  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
+                     n_cand < (int64_t(1) << 31) - TK_CHUNK_MAX && n_src < (int64_t(1) << 31),
+                 "tgnx_link_predictor_topk: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", (int)TK_DMAX);
+  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && (n_src == 0 || (z_src && out_val && out_idx)) &&
+                     (n_cand == 0 || z_cand),
+                 "tgnx_link_predictor_topk: null pointer");
+  TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_topk_ws_bytes(n_src, n_cand, d_in, D, k),
+                 "tgnx_link_predictor_topk: workspace too small");
+  if (n_src == 0) return TGNX_OK;
+  hipStream_t s = as_stream(stream);
+  const TopkWs w = topk_ws(ws, n_src, n_cand, D, k);
+  const int64_t ldh = ld_of(D);
+  const int chunk = chunk_of(n_src, n_cand);
+  const int64_t nc = ceil_div(n_cand, chunk), blocks = ceil_div(n_src, TK_TQ) * nc;
+  TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "tgnx_link_predictor_topk: n_src x n_cand beyond one launch's grid");
+  if (n_cand > 0) {
+    const size_t gbytes = ws_bytes - w.used;
+    int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
+    if (rc != TGNX_OK) return rc;
+    rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
+    if (rc != TGNX_OK) return rc;
+    hipLaunchKernelGGL(topk_pairs, dim3((unsigned)blocks), dim3(TK_BLOCK), pairs_smem(ldh, chunk), s, n_src, n_cand,
+                       (int)D, (int)ldh, chunk, (int)nc, (const float*)w.hs, (const float*)w.hd, w_out, b_out, (int)k,
+                       w.pval, w.pidx, out_all);
+    TGNX_LAUNCH_CHECK("topk_pairs");
+  }
+  // (n_cand = 0: no chunk, every slot is padding)
+  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src, (int)nc,
+                     (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_idx);
+  TGNX_LAUNCH_CHECK("topk_merge");
+  return TGNX_OK;
+}
+
+}  // extern "C"

@@ -328,6 +328,43 @@ at::Tensor predictor(const at::Tensor& z_src, const at::Tensor& z_dst, const at:
   return out;
 }
 
+// LinkPredictor over all (source, candidate) pairs with the top-k selection fused in (csrc/tgnx_topk.hip):
+// (val [B, k], idx [B, k] positions into z_cand, logits [B, C] or an empty tensor)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk(
+    const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src,
+    const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out,
+    int64_t k, bool sigmoid, bool return_scores) {
+  dev_tensor(z_src, at::kFloat, "z_src");
+  dev_tensor(z_cand, at::kFloat, "z_cand");
+  dev_tensor(w_src, at::kFloat, "w_src");
+  dev_tensor(w_dst, at::kFloat, "w_dst");
+  dev_tensor(w_out, at::kFloat, "w_out");
+  dev_tensor(b_out, at::kFloat, "b_out");
+  TORCH_CHECK(z_src.dim() == 2 && z_cand.dim() == 2 && z_src.size(1) == z_cand.size(1), "z_src [B, d] and z_cand [C, d]");
+  const int64_t B = z_src.size(0), C = z_cand.size(0), d_in = z_src.size(1), D = w_src.size(0);
+  TORCH_CHECK(w_src.dim() == 2 && w_src.size(1) == d_in && w_dst.dim() == 2 && w_dst.size(0) == D &&
+                  w_dst.size(1) == d_in,
+              "w_src / w_dst must be [D, d]");
+  TORCH_CHECK(w_out.numel() == D && b_out.numel() == 1, "w_out must have D entries and b_out one");
+  TORCH_CHECK(k >= 1 && k <= TGNX_TOPK_MAX, "k must be in [1, ", TGNX_TOPK_MAX, "], got ", k);
+  same_device(z_src, {&z_cand, &w_src, &w_dst, &w_out, &b_out});
+  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
+  const c10::OptionalDeviceGuard guard(z_src.device());
+  at::Tensor val = at::empty({B, k}, z_src.options());
+  at::Tensor idx = at::empty({B, k}, z_src.options().dtype(at::kLong));
+  at::Tensor all = return_scores ? at::empty({B, C}, z_src.options()) : at::empty({0}, z_src.options());
+  const size_t nb = tgnx_link_predictor_topk_ws_bytes(B, C, d_in, D, (int32_t)k);
+  at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
+  check_rc(tgnx_link_predictor_topk(B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(),
+                                    w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(),
+                                    b_out.data_ptr<float>(), (int32_t)k, sigmoid ? 1 : 0, val.data_ptr<float>(),
+                                    idx.data_ptr<int64_t>(), return_scores ? all.data_ptr<float>() : nullptr,
+                                    ws.data_ptr(), nb, cur_stream()),
+           "tgnx_link_predictor_topk");
+  return {val, idx, all};
+}
+
 void attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const c10::optional<at::Tensor>& e,
                const at::Tensor& indptr, int64_t heads) {
   dev_tensor(q, at::kFloat, "q");
@@ -782,6 +819,9 @@ TORCH_LIBRARY(tgnx, m) {
   m.def("gru_update_bwd(Tensor dh_out, Tensor x, Tensor h, Tensor w_ih, Tensor w_hh, Tensor? b_ih, Tensor? b_hh, "
         "int cell, int[] need) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
         &gru_update_bwd);
+  m.def("predictor_topk(Tensor z_src, Tensor z_cand, Tensor w_src, Tensor? b_src, Tensor w_dst, Tensor? b_dst, "
+        "Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores) -> (Tensor, Tensor, Tensor)",
+        &predictor_topk);
   m.def("predictor_bwd(Tensor dout, Tensor z_src, Tensor z_dst, Tensor w_src, Tensor? b_src, Tensor w_dst, "
         "Tensor? b_dst, Tensor w_out, Tensor b_out, bool sigmoid, int[] need) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",

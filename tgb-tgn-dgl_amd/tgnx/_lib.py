@@ -58,6 +58,8 @@ SIGNATURES = {
     "tgnx_tgn_scan_next": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_u64, c_vp]),
     "tgnx_tgn_eval_step": (ctypes.c_int, [P, P, c_i32, c_vp]),
     "tgnx_tgn_eval_step_resident": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_u64, P, c_vp]),
+    "tgnx_tgn_embed_max_nodes": (c_i64, [P]),
+    "tgnx_tgn_embed": (ctypes.c_int, [P, P, P, c_i64, P, P, c_vp]),
     "tgnx_tgn_flush": (ctypes.c_int, [P, P, P, ctypes.c_size_t, c_vp]),
     "tgnx_tgn_flush_scratch_bytes": (ctypes.c_size_t, [P]),
     "tgnx_tgn_apply_rows": (ctypes.c_int, [P, P, P, c_i64, c_vp]),
@@ -75,6 +77,9 @@ SIGNATURES = {
     "tgnx_link_predictor_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "tgnx_link_predictor": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, c_i32, P, P, c_sz,
                                            c_vp]),
+    "tgnx_link_predictor_topk_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i32]),
+    "tgnx_link_predictor_topk": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, c_i32, c_i32, P, P, P,
+                                                P, c_sz, c_vp]),
     "tgnx_edge_attn_fwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, c_vp]),
     "tgnx_edge_attn_bwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, P, P, P, P, c_vp]),
     # per-operator backward (tgnx_ops_bwd.hip)

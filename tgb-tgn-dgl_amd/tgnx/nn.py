@@ -195,6 +195,14 @@ class LinkPredictor(nn.Module):
         return ops.link_predictor(z_src, z_dst, self.lin_src.weight, self.lin_src.bias, self.lin_dst.weight,
                                   self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, sigmoid=True)
 
+    def topk(self, z_src, z_cand, k, return_scores=False):
+        """The k best rows of z_cand for every row of z_src: (val [n_src, k] sigmoid outputs, idx [n_src, k] positions
+        into z_cand[, logits [n_src, n_cand]]), all pairs scored and selected in one fused kernel (ops.link_topk; the
+        selection is on the logit, ties by lower position, -1 / 0 padding when k > n_cand).  No autograd."""
+        return ops.link_topk(z_src, z_cand, self.lin_src.weight, self.lin_src.bias, self.lin_dst.weight,
+                             self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, k, sigmoid=True,
+                             return_scores=return_scores)
+
 
 class TGNMemory(nn.Module):
     """modules/memory_module.py:25-215 over a device message store (csrc/tgnx_memstore.hip).

@@ -8,7 +8,8 @@ Ops: ring_reset / ring_sample / ring_insert (LastNeighborLoader, neighbor_loader
 tcsr_sample (TGL t-CSR, utils.py:73), gemm_f32 (MFMA fp32 GEMM), and the TGN modules' operators one call each
 (csrc/tgnx_ops.hip): msg_agg_last / msg_agg_mean (LastAggregator / MeanAggregator, modules/msg_agg.py:15-26),
 gru_update (TGNMemory's GRUCell / RNNCell, memory_module.py:70-78), predictor (LinkPredictor decoder.py:12-27;
-EdgePredictor model_utils.py:165-195) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
+EdgePredictor model_utils.py:165-195), predictor_topk (LinkPredictor over all pairs with the top-k selection fused
+in, csrc/tgnx_topk.hip; `link_topk` below) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
 emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function), time_encode (TimeEncoder)
 and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
 gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd, msg_agg_mean_bwd) sit
@@ -27,7 +28,7 @@ import torch
 
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
-       "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "edge_attn_fwd", "edge_attn_bwd",
+       "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "predictor_topk", "edge_attn_fwd", "edge_attn_bwd",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
@@ -155,6 +156,20 @@ def link_predictor(z_src, z_dst, w_src, b_src, w_dst, b_dst, w_out, b_out, sigmo
     c = lambda t: None if t is None else t.contiguous()  # noqa: E731
     return _LinkPredictor.apply(c(z_src), c(z_dst), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out), c(b_out),
                                 bool(sigmoid))
+
+
+@torch.no_grad()
+def link_topk(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, k, sigmoid=True, return_scores=False):
+    """The k best candidates of every source under LinkPredictor (decoder.py:12-27), scored over all n_src x n_cand
+    pairs and selected in the same kernel (tgnx_link_predictor_topk): no [n_src * n_cand, d] operand, no score
+    matrix handed to torch.topk.  Returns (val [n_src, k], idx [n_src, k]) and, with return_scores, the logits
+    [n_src, n_cand] the selection compared.  idx holds positions into z_cand, ordered by larger logit, equal logits
+    by lower position; val the logits, or their sigmoid (sigmoid=True); slots past n_cand hold idx -1 and val -inf
+    (0 with sigmoid).  The selection is always on the logit.  Inference only: no autograd."""
+    c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+    val, idx, logits = load().predictor_topk(c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out),
+                                             c(b_out), int(k), bool(sigmoid), bool(return_scores))
+    return (val, idx, logits) if return_scores else (val, idx)
 
 
 class _TimeEncode(torch.autograd.Function):

@@ -562,6 +562,64 @@ class TgnEngine:
         self._keep = negs
         return self.out_pos[:B], self.out_neg[:B * Kn].view(B, Kn), self.mrr[:B]
 
+    # ------------------------------------------------------------------ read-only inference
+    def embed_capacity(self) -> int:
+        """Nodes per tgnx_tgn_embed call: the eval root capacity min(N, max_batch * (2 + max_neg))."""
+        return int(_lib.lib().tgnx_tgn_embed_max_nodes(ctypes.byref(self.cfg)))
+
+    @torch.no_grad()
+    def embed(self, nodes, validate: bool = True) -> torch.Tensor:
+        """Embeddings [n, D] of `nodes` (any integer sequence / tensor; duplicates allowed) at the current stream
+        state, as an eval batch computes them before scoring: memory and last_update as stored, the ring sampled for
+        the node set, GraphAttentionEmbedding (tgnx_tgn_embed).  Read-only: memory, stores, ring, parameters and the
+        batch cursor are untouched (ctl[3], the generation stamp, advances by one per chunk), so eval and train go on
+        as if it had not been called; like every non-train call it makes the next resident step prepare its batch
+        again.  Nothing is flushed: after train steps call flush() first (as tgn_epoch.test does), or the stored
+        messages of the last batches are not in the memory rows read here.  Node sets beyond embed_capacity() run in
+        chunks.  validate: one host read checks the ids against [0, N) and raises ValueError; without it an id out
+        of range gets a zero row."""
+        self.finish()
+        self._prefetched = False
+        nodes = torch.as_tensor(nodes).to(self.dev, torch.long).contiguous().view(-1)
+        n, N = nodes.numel(), self.cfg.num_nodes
+        if validate and n and bool(((nodes < 0) | (nodes >= N)).any()):
+            raise ValueError(f"embed: node ids must be in [0, {N})")
+        out = torch.empty(n, self.cfg.mem_dim, dtype=torch.float32, device=self.dev)
+        cap = self.embed_capacity()
+        if cap <= 0:
+            raise RuntimeError(f"tgnx_tgn_embed_max_nodes: {_lib.lib().tgnx_last_error().decode()}")
+        b = self._buffers(0)
+        for a in range(0, n, cap):
+            m = min(cap, n - a)
+            _lib.call("tgnx_tgn_embed", ctypes.byref(self.cfg), ctypes.byref(b), nodes.data_ptr() + a * 8, m,
+                      out.data_ptr() + a * self.cfg.mem_dim * 4, 0, self._stream())
+        if n:
+            self.check()
+        return out
+
+    @torch.no_grad()
+    def recommend(self, src, k: int, candidates=None, return_scores: bool = False):
+        """For every source node the k candidates the model ranks highest at the current stream state:
+        (val [Q, k] sigmoid outputs, node_ids [Q, k][, logits [Q, C]]).  candidates: node ids (default: the engine's
+        dst_nodes when it has them, else every node).  Sources and candidates are embedded with embed() (read-only,
+        chunked), then scored over all pairs and selected in one fused kernel with the model's link_pred parameters
+        (ops.link_topk: ranked by logit, equal logits by the candidate's position in `candidates`).  k beyond the
+        candidate count pads with node id -1 and val 0."""
+        from . import ops
+        if candidates is None:
+            candidates = self.dst_nodes if self.dst_nodes is not None else \
+                torch.arange(self.cfg.num_nodes, device=self.dev)
+        cand = torch.as_tensor(candidates).to(self.dev, torch.long).contiguous().view(-1)
+        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        z = self.embed(torch.cat([src, cand]))
+        lp = self.model.link_pred
+        out = ops.link_topk(z[:src.numel()], z[src.numel():], lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight,
+                            lp.lin_dst.bias, lp.lin_final.weight, lp.lin_final.bias, k, sigmoid=True,
+                            return_scores=return_scores)
+        idx = out[1]
+        ids = torch.where(idx >= 0, cand[idx.clamp(min=0)], idx) if cand.numel() else idx
+        return (out[0], ids) + tuple(out[2:])
+
     # ------------------------------------------------------------------ resident eval pass
     def bind_eval_resident(self, split_lo: int, split_hi: int, batch: int, negs):
         """A validation / test pass over events [split_lo, split_hi) in batches of `batch`, resident on the device:

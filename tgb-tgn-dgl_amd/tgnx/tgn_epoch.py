@@ -16,6 +16,9 @@ backward, Adam.  test(): the first call after training switches the memory to ev
 memory_module.py:209-215); each batch scores [pos, negatives] with the batch-start state, then
 updates the stores, the memory and the ring in eval order.
 
+  recommend(model, neighbor_loader, src, k, candidates=None) -> (val [Q, k], node_ids [Q, k]): the k destinations
+      the trained model ranks highest for each source at the current stream state (TgnEngine.recommend; read-only)
+
 Reached through pyg_epoch_utils (shim) and through epoch_utils.train / test, which dispatch here for a
 {'memory', 'gnn', 'link_pred'} model: the reference script runs with only its model import swapped
 (pyg-mem-tgn.py:19 keeps `from epoch_utils import train, test`).
@@ -169,3 +172,19 @@ def test(model, feats, loader, neighbor_loader, neg_sampler, assoc, device, opti
     torch.cuda.synchronize(eng.dev)
     eng.check()
     return float(torch.stack(perf).mean()) if perf else float("nan")
+
+
+@torch.no_grad()
+def recommend(model, neighbor_loader, src, k, candidates=None):
+    """Top-k link recommendation with the engine train() / test() attached to the model: for every node of `src` the
+    k candidates (default: the engine's destination set) with the highest LinkPredictor output at the current stream
+    state, as (val [Q, k], node_ids [Q, k]).  Read-only (TgnEngine.recommend).  Straight after train() the memory is
+    switched to eval first, exactly as test() does (TGNMemory.train(False), memory_module.py:209-215)."""
+    eng = getattr(_owner(model), "_tgnx_engine", None)
+    if eng is None or eng.loader is not neighbor_loader:
+        raise RuntimeError("tgnx recommend: no engine bound to this model / neighbor_loader yet (run train() or test() "
+                           "first: they bind the event table)")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    return eng.recommend(src, k, candidates=candidates)
