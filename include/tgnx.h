@@ -538,6 +538,29 @@ int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg);
 int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
                    float* out_z /* [n, mem_dim] */, int64_t* n_invalid /* device, caller-zeroed, may be NULL */,
                    void* stream);
+/* Score-free ingestion: the state update of tgnx_tgn_eval_step for the batch ctl describes (as after
+ * tgnx_tgnn_advance(..., train = 0)), without negatives and without the forward that scores them — update_state in
+ * eval order (memory_module.py:126-138 with training == False: store the batch's messages, aggregate and run the
+ * memory updater over src ∪ dst, write memory and last_update) and the ring insert (neighbor_loader.insert).
+ * buf->neg, out_pos, out_neg and mrr are not read and may be NULL.  Afterwards memory, last_update, the stores, the
+ * ring, node_gen and the ctl words an eval step moves (none beyond what the advance set; SUM_E / SUM_S grow by 0 and
+ * by |src ∪ dst|, not by the eval step's sample) are what tgnx_tgn_eval_step leaves for the same batch with any
+ * negatives.
+ * emb_in_msg == 0, 6 launches at either `layers` (the eval step has 11 at 1 hop): tgn_observe_mark (one thread per
+ * endpoint: node_gen stamp, kval = 0, centre + node bit; no ring row is read, no neighbour or candidate is marked),
+ * tgn_scan (update list = centres = nodes, and the insert / store plans), tgn_update (stores + ring), the aggregation
+ * and the updater GEMM of the update list, tgn_update (memory write).  No edge / projection GEMM, no attention, no
+ * predictor, no score: no work proportional to Kn or to the ring width.
+ * emb_in_msg != 0 (DyRep embedding messages, 1 hop): the stored messages carry the eval forward's embeddings of
+ * src ∪ dst, so after tgn_observe_mark the eval launches up to tgn_attn_fwd run for the 2B endpoint roots (tgn_mark
+ * with no negative slots), then the same update; still no predictor or score launch.
+ * B == 0 launches work that returns at once and changes no state (the marking clears the scan's counts, so no
+ * earlier batch's update runs again).  A batch beyond max_batch or the event table, or an endpoint outside
+ * [0, num_nodes), sets TGNX_CTL_ERR bit 4 and the step does nothing further.  No host synchronisation, no allocation.
+ * One device only (no row exchange).  assoc and the workspace are scratch as for every step: a pipelined / parity-set
+ * train step after it must run with prefetched = 0.
+ * Test: tests/test_gpu_tgn_observe.py (against the eval step bit for bit, and against the oracle's update_state). */
+int tgnx_tgn_observe_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, void* stream);
 
 /* train(False): update the memory of every node from its stored messages, clear the stores
  * (memory_module.py:209-215).  Every row is computed from the pre-flush state (:212 updates arange(N) at

@@ -817,6 +817,66 @@ __global__ void __launch_bounds__(256) tgn_embed_mark(Ctx c, const int* own, con
   }
 }
 
+// ------------------------------------------------------------------ score-free ingestion (tgnx_tgn_observe_step)
+// The marking of a batch that is only observed: update_state and the ring insert need the update list src ∪ dst and
+// the batch's plans, not a sample.  One thread per endpoint (2B of them), no ring row is read:
+//   node_gen[v] = GEN        the scan's update-list test;
+//   kval[v] = 0              a centre without sampled edges (E = 0; a later forward's marking walks v again and
+//                            writes its own count, so no stale count of an earlier step is left for it either);
+//   centre and node bit of v (with their summary bits on a graph the scan does not walk directly): every endpoint is
+//                            a centre whose only sampled node is itself, so R = M = U = |src ∪ dst| <= Ucap and
+//                            upd = cent = nid.  No root bit: there is no forward, and the scan's root pass then
+//                            writes R1 = E1 = 0.
+// A graph the scan walks directly gets the block's bits in one LDS bitmap first (the centre and node bitmaps take the
+// same bits), ORed into the global words at the end, as mark_body's LDS-local form does.
+// Thread 0 clears the scan's counts before anything else: with B = 0 (or the error flag set) the scan returns at once,
+// and the launches after it size their work from the counts — a previous batch's would run its memory update again
+// (tgn_eval_cursor takes the same care).  A batch outside [0, max_batch] x the event table, or an endpoint outside
+// [0, N), sets error bit 4 instead of being used as an index; every later launch of the step then returns.
+__global__ void __launch_bounds__(256) tgn_observe_mark(Ctx c) {
+  __shared__ uint32_t lb[MARK_LDS_WORDS];
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    c.cnt[CNT_R] = c.cnt[CNT_M] = c.cnt[CNT_E] = c.cnt[CNT_U] = c.cnt[CNT_LIST] = c.cnt[CNT_R1] = c.cnt[CNT_E1] = 0;
+  const int64_t Bw = c.ctl[TGNX_CTL_B], start = c.ctl[TGNX_CTL_BATCH_START];
+  if (Bw == 0 || c.ctl[TGNX_CTL_ERR] != 0) return;
+  unsigned long long* err = reinterpret_cast<unsigned long long*>(c.errw);
+  if (Bw < 0 || Bw > c.Bmax || start < 0 || start + Bw > c.nev) {  // (block-uniform)
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, 4ull);
+    return;
+  }
+  const int B = (int)Bw, gen = (int)c.ctl[TGNX_CTL_GEN], W = (int)c.words;
+  const bool direct = scan_direct(c.words);  // (block-uniform)
+  if (direct) {
+    for (int x = threadIdx.x; x < W; x += blockDim.x) lb[x] = 0u;
+    __syncthreads();
+  }
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < 2 * B; q += gridDim.x * blockDim.x) {
+    const int64_t v = q < B ? c.ev_src[start + q] : c.ev_dst[start + q - B];
+    if (v < 0 || v >= c.N) {
+      atomicOr(err, 4ull);
+      continue;
+    }
+    c.node_gen[v] = gen;
+    c.kval[v] = 0;
+    if (direct) {
+      atomicOr(&lb[v >> 5], 1u << (v & 31));
+    } else {
+      mark_node(c.cb, c.cbs, v);
+      mark_node(c.nb, c.nbs, v);
+    }
+  }
+  if (direct) {
+    __syncthreads();
+    for (int x = threadIdx.x; x < W; x += blockDim.x) {
+      const uint32_t a = lb[x];
+      if (a) {
+        atomicOr(&c.cb[x], a);
+        atomicOr(&c.nb[x], a);
+      }
+    }
+  }
+}
+
 // message-store plan of a batch: (node << 33 | dir << 32 | i), dir 0 = as source (msg_s_store),
 // 1 = as destination (msg_d_store); sorted, each (node, dir) run lists its events in batch order
 // (memory_module.py:188-191 with a stable sort): plan_part(which = 1) below.
@@ -6065,6 +6125,58 @@ int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, cons
   }
   tgn_embed_gather<<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
   TGNX_LAUNCH_CHECK("tgn_embed_gather");
+  return TGNX_OK;
+}
+
+// eval_step_impl's state update without its forward: see tgn_observe_mark
+int tgnx_tgn_observe_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, void* stream) {
+  Ctx c;
+  Caps k;
+  WsLay W;
+  TGNX_CHECK_ARG(cfg && buf, "tgnx_tgn_observe_step: null config or buffers");
+  int rc = make_ctx(cfg, buf, 0, c, k, W);  // Kn = 0: a marking of the batch has no negative slots
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  tgn_observe_mark<<<gridn(2 * k.B, 256), 256, 0, s>>>(c);
+  TGNX_LAUNCH_CHECK("tgn_observe_mark");
+  if (c.emb) {
+    // DyRep embedding messages (1 hop): the stored messages carry the eval forward's embeddings of src ∪ dst, so the
+    // forward runs for the 2B endpoint roots — the eval marking with no negative slots adds their ring rows to the
+    // endpoints marked above — up to the attention; no predictor, no score
+    const float* P = c.params;
+    const int D = c.D, HC = c.HC, d = c.d;
+    const int Rq = (int)std::min<int64_t>(c.N, 2 * (int64_t)k.B);
+    const int Mq = (int)std::min<int64_t>(c.N, (int64_t)Rq * (c.K + 1));
+    const int Eq = Rq * c.K;
+    const int nmark = gridn((int64_t)k.B * 2 * 16, 256);
+    tgn_mark<false><<<nmark, 256, 0, s>>>(c, nmark);
+    TGNX_LAUNCH_CHECK("tgn_mark");
+    tgn_scan<false><<<1 + 2 * c.pplan, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
+    TGNX_LAUNCH_CHECK("tgn_scan");
+    const int nedge = gridn((int64_t)Rq * c.K, 4, 4096);
+    tgn_agg_emit<-1><<<nedge + gridn(Mq, 256), 256, 0, s>>>(c, 1, nedge, nullptr, nullptr, 0, 0);
+    TGNX_LAUNCH_CHECK("tgn_emit");
+    gemmN_launch(s,
+                 gemm_job<G32>(gemm_shape<G32>(Eq, HC, D + d, c.cnt + CNT_E), LoadEdgeAttr{c.encE, c.e_id, c.ev_msg, D, d},
+                               LoadRowK{P + c.L.we, HC, D + d, D + d}, EpiStore{c.Ep, nullptr, HC, 0}, (float*)nullptr),
+                 gemm_job<G32>(gemm_shape<G32>(Mq, 4 * HC, D, c.cnt + CNT_M), LoadZ{c.Z0, c.mem, c.nid, D, 1},
+                               LoadProjW{P + c.L.wq, c.L.pw, HC, D}, EpiProj{P + c.L.bq, c.L.pb, c.P, HC},
+                               (float*)nullptr));
+    TGNX_LAUNCH_CHECK("tgn_edge_proj");
+    tgn_attn_fwd<false><<<gridn(Rq, 4, 1 << 20), 256, 0, s>>>(c);
+    TGNX_LAUNCH_CHECK("tgn_attn_fwd");
+  } else {
+    tgn_scan<false><<<1 + 2 * c.pplan, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
+    TGNX_LAUNCH_CHECK("tgn_scan");
+  }
+  // update_state in eval order and the ring insert: eval_step_impl's last three calls
+  const int nst = gridn(2 * k.B, 256), nring = gridn(2 * k.B, 4);
+  tgn_update<<<nst + nring, 256, 0, s>>>(c, 0, nst, 1, nullptr, nullptr, 0, 0);
+  TGNX_LAUNCH_CHECK("tgn_store_insert");
+  gru_list(c, k, c.upd, c.cnt + CNT_U, 0, 0, k.Ucap, s, c.emb != 0);
+  TGNX_LAUNCH_CHECK("tgn_gru_update");
+  tgn_update<<<gridn(k.Ucap, 4, 1024), 256, 0, s>>>(c, gridn(k.Ucap, 4, 1024), 0, 1, c.upd, c.cnt + CNT_U, 0, 0);
+  TGNX_LAUNCH_CHECK("tgn_memory_write");
   return TGNX_OK;
 }
 

@@ -60,6 +60,7 @@ SIGNATURES = {
     "tgnx_tgn_eval_step_resident": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_u64, P, c_vp]),
     "tgnx_tgn_embed_max_nodes": (c_i64, [P]),
     "tgnx_tgn_embed": (ctypes.c_int, [P, P, P, c_i64, P, P, c_vp]),
+    "tgnx_tgn_observe_step": (ctypes.c_int, [P, P, c_vp]),
     "tgnx_tgn_flush": (ctypes.c_int, [P, P, P, ctypes.c_size_t, c_vp]),
     "tgnx_tgn_flush_scratch_bytes": (ctypes.c_size_t, [P]),
     "tgnx_tgn_apply_rows": (ctypes.c_int, [P, P, P, c_i64, c_vp]),

@@ -290,6 +290,36 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+def grown_capacity(cap: int, need: int) -> int:
+    """Row capacity of the event table for `need` rows when it holds `cap`: unchanged while they fit, else the larger
+    of `need` and 1.5 x cap — geometric, so n appended rows cost O(n) copied rows in all."""
+    cap, need = int(cap), int(need)
+    if cap < 0 or need < 0:
+        raise ValueError(f"grown_capacity: negative row count ({cap}, {need})")
+    return cap if need <= cap else max(need, cap + cap // 2)
+
+
+def check_event_rows(n_src: int, n_dst: int, n_t: int, msg_shape: tuple, msg_dim: int) -> int:
+    """The row count of an appended chunk, or ValueError: src, dst, t of one length n and msg [n, msg_dim]."""
+    n = int(n_src)
+    if int(n_dst) != n or int(n_t) != n:
+        raise ValueError(f"append_events: src, dst, t must have one length, got {n_src}, {n_dst}, {n_t}")
+    if len(msg_shape) != 2 or tuple(int(x) for x in msg_shape) != (n, int(msg_dim)):
+        raise ValueError(f"append_events: msg must be [n, msg_dim] = [{n}, {msg_dim}], got {tuple(msg_shape)}")
+    return n
+
+
+def check_observe_args(start: int, B: int, max_batch: int, num_events: int, world: int = 1) -> None:
+    """ValueError unless rows [start, start + B) are a batch observe() can take: 0 <= B <= max_batch, inside the
+    table's valid rows, one device."""
+    if world > 1:
+        raise ValueError("observe: one device only (world > 1 is not built)")
+    if B < 0 or B > max_batch:
+        raise ValueError(f"observe: B = {B} outside [0, max_batch = {max_batch}]")
+    if start < 0 or start + B > num_events:
+        raise ValueError(f"observe: rows [{start}, {start + B}) outside the event table ({num_events} events)")
+
+
 EXCHANGE_MODES = ("fused", "split")
 
 
@@ -350,6 +380,9 @@ class TgnEngine:
         self.msg = ev["msg"].to(self.dev, torch.float32).contiguous()
         if self.src.numel() > cfg.num_events:
             raise ValueError("event table larger than cfg.num_events")
+        # the table's allocations (capacity rows; append_events grows them): src / dst / t / msg above are their first
+        # num_events rows
+        self._tab = (self.src, self.dst, self.t, self.msg)
         nb = _lib.lib().tgnx_tgn_ws_bytes(ctypes.byref(cfg))
         if nb == 0:
             raise RuntimeError(f"tgnx_tgn_ws_bytes: {_lib.lib().tgnx_last_error().decode()}")
@@ -561,6 +594,115 @@ class TgnEngine:
         _lib.call("tgnx_tgn_eval_step", ctypes.byref(self.cfg), ctypes.byref(b), Kn, self._stream())
         self._keep = negs
         return self.out_pos[:B], self.out_neg[:B * Kn].view(B, Kn), self.mrr[:B]
+
+    # ------------------------------------------------------------------ score-free ingestion
+    @property
+    def num_events(self) -> int:
+        """Valid rows of the event table (cfg.num_events is its capacity, which sizes the store arena)."""
+        return int(self.src.numel())
+
+    @property
+    def event_capacity(self) -> int:
+        return int(self._tab[0].numel())
+
+    def _set_rows(self, n: int):
+        self.src, self.dst, self.t, self.msg = (x[:n] for x in self._tab)
+
+    def reserve_events(self, n: int) -> None:
+        """Capacity for at least n event rows, ahead of time (append_events grows it geometrically otherwise).  On
+        growth the four table tensors are reallocated and copied, the model's store arena grows with them
+        (TGNModel.ensure_events keeps the stored words), neg_train and the output log are resized, cfg.num_events
+        follows the capacity, and everything that captured a pointer is dropped as ensure_neg drops it: the resident
+        binding is made again (its plan table rebuilt), the captured train and eval graphs are gone (capture again)."""
+        n = int(n)
+        old = self._tab
+        if n <= old[0].numel():
+            return
+        self.finish()
+        torch.cuda.synchronize(self.dev)
+        rows = self.num_events
+        new = tuple(torch.zeros((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=self.dev) for x in old)
+        for a, b in zip(new, old):
+            a[:rows].copy_(b[:rows])
+        self._tab = new
+        self._set_rows(rows)
+        self.model.ensure_events(n)
+        cap = int(self.cfg.num_events)
+        for name in ("neg_train", "out_ev"):
+            x = getattr(self, name)
+            if x is not None and x.shape[0] < cap:
+                y = torch.zeros((cap,) + tuple(x.shape[1:]), dtype=x.dtype, device=self.dev)
+                y[:x.shape[0]].copy_(x)
+                setattr(self, name, y)
+        self._prefetched = False
+        self._graphs = None                                   # captured pointers are stale
+        self._group = None
+        if hasattr(self, "_res_buf"):
+            self.bind_resident(*self._res, dropout=bool(self._res_drop))   # (drops and rebuilds the plan table)
+        else:
+            self._rebind_eval()
+
+    @torch.no_grad()
+    def append_events(self, src, dst, t, msg, validate: bool = True):
+        """Append rows to the device event table; returns (start, n): they are rows [start, start + n).  dtypes are
+        converted as the constructor converts them; msg must be [n, msg_dim].  validate: one host read checks the
+        node ids against [0, N) and raises ValueError before anything is written; without it (no host read) ids are
+        clamped into [0, N), so an id out of range never reaches a kernel as an index.  Appending alone moves no
+        stream state: observe() / observe_range() / eval and train batches over the new rows do."""
+        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        dst = torch.as_tensor(dst).to(self.dev, torch.long).contiguous().view(-1)
+        t = torch.as_tensor(t).to(self.dev, torch.float32).contiguous().view(-1)
+        msg = torch.as_tensor(msg).to(self.dev, torch.float32).contiguous()
+        n = check_event_rows(src.numel(), dst.numel(), t.numel(), tuple(msg.shape), self.cfg.msg_dim)
+        N = self.cfg.num_nodes
+        if validate:
+            if n and bool(((src < 0) | (src >= N) | (dst < 0) | (dst >= N)).any()):
+                raise ValueError(f"append_events: node ids must be in [0, {N})")
+        else:
+            src, dst = src.clamp(0, N - 1), dst.clamp(0, N - 1)
+        start = self.num_events
+        if n == 0:
+            return start, 0
+        self.finish()
+        self._prefetched = False
+        self.reserve_events(grown_capacity(self.event_capacity, start + n))
+        for buf, rows in zip(self._tab, (src, dst, t, msg)):
+            buf[start:start + n].copy_(rows)
+        self._set_rows(start + n)
+        return start, n
+
+    def observe(self, start: int, B: int):
+        """Advance memory, last_update, the message stores and the ring over resident rows [start, start + B) without
+        scoring anything (tgnx_tgn_observe_step): the state afterwards is what eval_batch(start, B, negs) leaves for
+        any negatives.  No negatives, no outputs.  Asynchronous like every step: check() reads the error flags."""
+        start, B = int(start), int(B)
+        check_observe_args(start, B, self.cfg.max_batch, self.num_events, self.world)
+        self.advance(start, B, False)
+        b = self._buffers(0)
+        b.xrows, b.xcap = 0, 0
+        _lib.call("tgnx_tgn_observe_step", ctypes.byref(self.cfg), ctypes.byref(b), self._stream())
+
+    def observe_range(self, lo: int, hi: int, batch=None):
+        """observe() over resident rows [lo, hi) in batches of `batch` (default cfg.max_batch), the last one partial:
+        the replay that rebuilds memory, stores and ring from history — after loading a checkpoint, say — without
+        scoring negatives.  Batching is semantic in TGN (the messages of one batch do not see each other): the result
+        is that of an eval pass over the same rows with the same batching."""
+        lo, hi = int(lo), int(hi)
+        batch = int(self.cfg.max_batch if batch is None else batch)
+        if not (0 <= lo <= hi <= self.num_events) or not (0 < batch <= self.cfg.max_batch):
+            raise ValueError(f"observe_range: rows [{lo}, {hi}) batch {batch} outside the event table "
+                             f"({self.num_events} events) / max_batch ({self.cfg.max_batch})")
+        for a in range(lo, hi, batch):
+            self.observe(a, min(batch, hi - a))
+
+    def observe_events(self, src, dst, t, msg, batch=None, validate: bool = True):
+        """append_events, then observe the new rows in batches of `batch` (default cfg.max_batch) — batched per call:
+        two calls of 30 events at batch 50 are two batches of 30.  Returns (start, n)."""
+        if self.world > 1:
+            raise ValueError("observe_events: one device only (world > 1 is not built)")
+        start, n = self.append_events(src, dst, t, msg, validate=validate)
+        self.observe_range(start, start + n, batch)
+        return start, n
 
     # ------------------------------------------------------------------ read-only inference
     def embed_capacity(self) -> int:

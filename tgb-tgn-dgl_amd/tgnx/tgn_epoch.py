@@ -18,6 +18,9 @@ updates the stores, the memory and the ring in eval order.
 
   recommend(model, neighbor_loader, src, k, candidates=None) -> (val [Q, k], node_ids [Q, k]): the k destinations
       the trained model ranks highest for each source at the current stream state (TgnEngine.recommend; read-only)
+  observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
+      table and taken into memory, stores and ring as test() batches would leave them, without negatives or scores
+      (TgnEngine.observe_events)
 
 Reached through pyg_epoch_utils (shim) and through epoch_utils.train / test, which dispatch here for a
 {'memory', 'gnn', 'link_pred'} model: the reference script runs with only its model import swapped
@@ -188,3 +191,22 @@ def recommend(model, neighbor_loader, src, k, candidates=None):
         eng.flush()
         eng._mode_train = False
     return eng.recommend(src, k, candidates=candidates)
+
+
+@torch.no_grad()
+def observe(model, neighbor_loader, src, dst, t, msg, batch=None):
+    """Take new interactions into the stream state of the engine train() / test() attached to the model, without
+    scoring them: the rows are appended to the resident event table, then memory, message stores and ring advance over
+    them in batches of `batch` (default: the model's max_batch) exactly as test() batches would leave them
+    (TgnEngine.observe_events; no negatives, no outputs).  Straight after train() the memory is switched to eval first,
+    as test() and recommend() do.  Returns (start, n): the events are rows [start, start + n) of the table."""
+    eng = getattr(_owner(model), "_tgnx_engine", None)
+    if eng is None or eng.loader is not neighbor_loader:
+        raise RuntimeError("tgnx observe: no engine bound to this model / neighbor_loader yet (run train() or test() "
+                           "first: they bind the event table)")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    start, n = eng.observe_events(src, dst, t, msg, batch=batch)
+    neighbor_loader.cur_e_id = start + n
+    return start, n
