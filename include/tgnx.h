@@ -562,6 +562,37 @@ int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, cons
  * Test: tests/test_gpu_tgn_observe.py (against the eval step bit for bit, and against the oracle's update_state). */
 int tgnx_tgn_observe_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, void* stream);
 
+/* Event-table compaction (csrc/tgnx_compact.hip): retire every row of the event table that nothing
+ * references and renumber the survivors order-preservingly (new id = rank among the live rows).  A row e of the
+ * num_events valid rows (cfg->num_events is the capacity) is live when a ring slot with nbr != -1 holds it, when a
+ * node's s- or d-store run holds it, or when e >= upto.  Two calls, because the caller sizes the new allocations
+ * from one number in between; ws is tgnx_tgn_compact_ws_bytes(cfg, num_events) bytes, 16-B aligned, not zeroed, and
+ * must pass unchanged from plan to apply.  Its first 8 int64 are the plan's record: [0] n_live, [1] live arena
+ * entries (the sum of the walkable run lengths), [2] bad ids, [4] num_events, [5] upto.
+ * tgnx_tgn_compact_plan (5 launches) writes only ws: the live bitmap, the exclusive prefix of its popcounts (a
+ * fixed-order multi-workgroup integer scan: deterministic) and of the nodes' run lengths, and the record.  An event
+ * id outside [0, num_events) in a ring slot or an arena entry, and a run {off, cnt} with cnt < 0 or outside the arena
+ * words [0, 2 * num_events), are never used as an index: they are counted into record[2].  Reads buf->nbr / eid /
+ * store; buf->ctl must be set (apply writes it).
+ * tgnx_tgn_compact_apply (4 launches) gathers src / dst / t / msg of the live rows into the new table (capacity
+ * new_capacity rows; msg rows move as 16-byte pieces with a scalar tail), writes kept[new] = old (kept_len slots),
+ * remaps buf->eid in place (slots with nbr == -1 untouched), writes the repacked node table and arena into new_store
+ * (4 * num_nodes + 2 * new_capacity int64, zero-filled by the caller: node by node, s run then d run; counts
+ * unchanged, empty runs at offset 0) and sets ctl BATCH_START = CUR_EID = n_live; no other ctl word changes.  Its
+ * kernels check the record first and store nothing when it was made for another row count, counted a bad id, or
+ * n_live exceeds new_capacity or kept_len: the caller reads the record after the plan and does not call apply then.
+ * Order-preserving renumbering keeps every comparison of event ids (the ring merge ranks by e_id, the stores keep
+ * batch order, later rows get ids >= n_live), and the repacked runs fit below 2 * n_live, where the next batch writes.
+ * Null or mis-sized arguments: TGNX_EINVAL, nothing launched; num_events >= 2^30: TGNX_ETOOBIG.  One device only.
+ * Test: tests/test_gpu_tgn_compact.py. */
+size_t tgnx_tgn_compact_ws_bytes(const tgnx_tgn_config* cfg, int64_t num_events);
+int tgnx_tgn_compact_plan(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t num_events, int64_t upto,
+                          void* ws, size_t ws_bytes, void* stream);
+int tgnx_tgn_compact_apply(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t num_events,
+                           int64_t new_capacity, int64_t* new_src, int64_t* new_dst, float* new_t, float* new_msg,
+                           int64_t* new_store, int64_t* kept, int64_t kept_len, const void* ws, size_t ws_bytes,
+                           void* stream);
+
 /* train(False): update the memory of every node from its stored messages, clear the stores
  * (memory_module.py:209-215).  Every row is computed from the pre-flush state (:212 updates arange(N) at
  * once).  Graphs with more nodes than the workspace's GRU row capacity run in chunks that read a snapshot

@@ -320,6 +320,78 @@ def check_observe_args(start: int, B: int, max_batch: int, num_events: int, worl
         raise ValueError(f"observe: rows [{start}, {start + B}) outside the event table ({num_events} events)")
 
 
+def check_compact_args(num_events: int, upto=None, capacity=None, world: int = 1) -> int:
+    """The resolved `upto` of compact_events (default num_events), or ValueError: one device, 0 <= upto <= num_events,
+    capacity (when given) at least 1."""
+    if world > 1:
+        raise ValueError("compact_events: one device only (world > 1 is not built)")
+    num_events = int(num_events)
+    upto = num_events if upto is None else int(upto)
+    if upto < 0 or upto > num_events:
+        raise ValueError(f"compact_events: upto = {upto} outside [0, num_events = {num_events}]")
+    if capacity is not None and int(capacity) < 1:
+        raise ValueError(f"compact_events: capacity = {capacity} must be at least 1")
+    return upto
+
+
+def compact_capacity(n_live: int, capacity=None) -> int:
+    """Row capacity of the compacted table: `capacity` when given (ValueError below n_live), else what grown_capacity
+    gives a full table of n_live rows for one more row — max(n_live + 1, 1.5 x n_live) — so that the next append does
+    not reallocate at once."""
+    n_live = int(n_live)
+    if n_live < 0:
+        raise ValueError(f"compact_events: negative live row count {n_live}")
+    if capacity is not None:
+        if int(capacity) < max(n_live, 1):
+            raise ValueError(f"compact_events: capacity = {capacity} below the {n_live} live rows")
+        return int(capacity)
+    return grown_capacity(n_live, n_live + 1)
+
+
+STREAM_STATE_FORMAT = 1
+STREAM_FINGERPRINT = ("num_nodes", "ring", "mem_dim", "msg_dim")
+# key -> shape in terms of (N, K, D, d, n = num_events); the ints of the dict are format, the fingerprint, num_events
+STREAM_STATE_TENSORS = {
+    "src": lambda N, K, D, d, n: (n,), "dst": lambda N, K, D, d, n: (n,), "t": lambda N, K, D, d, n: (n,),
+    "msg": lambda N, K, D, d, n: (n, d),
+    "memory": lambda N, K, D, d, n: (N, D), "last_update": lambda N, K, D, d, n: (N,),
+    "node_gen": lambda N, K, D, d, n: (N,),
+    "store_nodes": lambda N, K, D, d, n: (N, 4), "store_arena": lambda N, K, D, d, n: (2 * n,),
+    "neighbors": lambda N, K, D, d, n: (N, K), "e_id": lambda N, K, D, d, n: (N, K), "ring_t": lambda N, K, D, d, n: (N, K),
+    "ctl": lambda N, K, D, d, n: (24,),
+}
+STREAM_STATE_KEYS = ("format",) + STREAM_FINGERPRINT + ("num_events",) + tuple(STREAM_STATE_TENSORS)
+
+
+def stream_fingerprint(cfg) -> dict:
+    """What a stream state must share with the engine that loads it."""
+    return {k: int(getattr(cfg, k)) for k in STREAM_FINGERPRINT}
+
+
+def check_stream_state(state, fingerprint: dict) -> int:
+    """num_events of a stream_state() dict, or ValueError: format 1, the engine's fingerprint, every key present and
+    every tensor of the shape the ints imply.  Reads shapes only (no tensor contents, nothing on a device)."""
+    if not isinstance(state, dict) or "format" not in state:
+        raise ValueError("load_stream_state: not a stream_state() dict (no 'format')")
+    if state["format"] != STREAM_STATE_FORMAT:
+        raise ValueError(f"load_stream_state: format {state['format']!r}, this build reads {STREAM_STATE_FORMAT}")
+    missing = [k for k in STREAM_STATE_KEYS if k not in state]
+    if missing:
+        raise ValueError(f"load_stream_state: missing keys {missing}")
+    got = {k: int(state[k]) for k in STREAM_FINGERPRINT}
+    if got != {k: int(fingerprint[k]) for k in STREAM_FINGERPRINT}:
+        raise ValueError(f"load_stream_state: the state's fingerprint {got} is not the engine's {dict(fingerprint)}")
+    n = int(state["num_events"])
+    if n < 0:
+        raise ValueError(f"load_stream_state: num_events = {n}")
+    dims = (got["num_nodes"], got["ring"], got["mem_dim"], got["msg_dim"], n)
+    for k, shape in STREAM_STATE_TENSORS.items():
+        have = tuple(int(x) for x in getattr(state[k], "shape", (-1,)))
+        if have != tuple(shape(*dims)):
+            raise ValueError(f"load_stream_state: {k} has shape {have}, expected {tuple(shape(*dims))}")
+    return n
+
+
 EXCHANGE_MODES = ("fused", "split")
 
 
@@ -359,7 +431,12 @@ class TgnEngine:
     the stores, inside its last launch.  Every other engine call, a loader version change, model.load_state_dict(),
     model.settle() / state_dict() and model.invalidate_prefetch() make the next step prepare its batch again.  A raw
     tensor write to memory / last_update / the stores between two resident steps without one of these is seen by the
-    GRU's hidden-state operand but not by the pre-gathered message rows: call invalidate_prefetch() after it."""
+    GRU's hidden-state operand but not by the pre-gathered message rows: call invalidate_prefetch() after it.
+
+    A long-running stream (world 1): compact_events() retires the event rows that neither the ring nor a message
+    store references and renumbers the rest in order, so the device footprint follows the live rows instead of the
+    stream's length; stream_state() / load_stream_state() checkpoint the table, memory, stores, ring and ctl.  Both
+    drop the resident bindings, the plan table and the captured graphs: bind again in the new numbering."""
 
     def __init__(self, model: TGNModel, loader, events: dict, optimizer: TgnAdam | None = None,
                  dst_nodes=None, seed: int = 0, rank: int = 0, world: int = 1, data_parallel: bool | None = None):
@@ -703,6 +780,151 @@ class TgnEngine:
         start, n = self.append_events(src, dst, t, msg, validate=validate)
         self.observe_range(start, start + n, batch)
         return start, n
+
+    # ------------------------------------------------------------------ compaction and stream-state checkpoints
+    def _drop_bindings(self):
+        """Forget everything that captured a pointer or names a row range: the captured train and eval graphs, the
+        plan table, the resident train and eval bindings (not made again: the caller binds again) and the drop-in
+        loops' record of what they bound."""
+        self._prefetched = False
+        self._graphs = None
+        self._group = None
+        self._release_plan_table()
+        for a in ("_res_buf", "_buf_ref", "_res", "_res_drop", "_res_fused", "_f", "_cfg_ref", "_ctl_p", "_pending",
+                  "_ev_buf", "_ev_buf_ref", "_ev_negs", "_ev_rr", "_keep"):
+            self.__dict__.pop(a, None)
+        self._ev = None
+        self._ev_graphs = None
+        for a in ("_bound", "_eval_bound"):          # (tgn_epoch.train / test: bind again on their next call)
+            if a in self.__dict__:
+                setattr(self, a, None)
+
+    def _install_table(self, tab, rows: int, store: torch.Tensor):
+        """Fresh table allocations of capacity tab[0].shape[0] with `rows` valid rows, and a fresh store sized for it:
+        cfg.num_events, neg_train and out_ev follow the capacity (re-zeroed: their rows belong to the old numbering)."""
+        cap = int(tab[0].shape[0])
+        m = self.model
+        self._tab = tuple(tab)
+        self._set_rows(rows)
+        m.store = store
+        m.cfg.num_events = m.num_events = cap
+        self.neg_train = torch.zeros(cap, dtype=torch.long, device=self.dev)
+        if self.out_ev is not None:
+            self.out_ev = torch.zeros((cap,) + tuple(self.out_ev.shape[1:]), dtype=self.out_ev.dtype, device=self.dev)
+        self.loader.cur_e_id = rows
+        self.loader.version = getattr(self.loader, "version", 0) + 1
+
+    def _compact_plan(self, upto: int):
+        """tgnx_tgn_compact_plan over the current table; returns (workspace, n_live, live arena entries, bad ids)
+        after one host read.  Writes only the workspace."""
+        nev = self.num_events
+        nb = int(_lib.lib().tgnx_tgn_compact_ws_bytes(ctypes.byref(self.cfg), nev))
+        if nb == 0:
+            raise RuntimeError(f"tgnx_tgn_compact_ws_bytes: {_lib.lib().tgnx_last_error().decode()}")
+        ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+        _lib.call("tgnx_tgn_compact_plan", ctypes.byref(self.cfg), ctypes.byref(self._buffers(0)), nev, int(upto), _p(ws),
+                  nb, self._stream())
+        rec = ws[:64].view(torch.int64).tolist()
+        return ws, int(rec[0]), int(rec[1]), int(rec[2])
+
+    def _compact_apply(self, ws: torch.Tensor, n_live: int, cap: int) -> torch.Tensor:
+        """tgnx_tgn_compact_apply into fresh allocations of `cap` rows, then the engine's tensors are swapped."""
+        old, N = self._tab, self.cfg.num_nodes
+        new = tuple(torch.zeros((cap,) + tuple(x.shape[1:]), dtype=x.dtype, device=self.dev) for x in old)
+        store = torch.zeros(4 * N + 2 * cap, dtype=torch.long, device=self.dev)
+        kept = torch.empty(n_live, dtype=torch.long, device=self.dev)
+        keep = torch.empty(1, dtype=torch.long, device=self.dev) if n_live == 0 else kept   # (a non-null pointer)
+        _lib.call("tgnx_tgn_compact_apply", ctypes.byref(self.cfg), ctypes.byref(self._buffers(0)), self.num_events, cap,
+                  _p(new[0]), _p(new[1]), _p(new[2]), _p(new[3]), _p(store), _p(keep), n_live, _p(ws), ws.numel(),
+                  self._stream())
+        self._install_table(new, n_live, store)
+        return kept
+
+    @torch.no_grad()
+    def compact_events(self, upto=None, capacity=None) -> torch.Tensor:
+        """Retire every row of the device event table that nothing references and renumber the survivors in order
+        (new id = rank among the live rows).  Returns kept, a LongTensor [n_live] of the surviving rows' old ids
+        (kept[new] = old), with which a caller translates its own records.
+
+        A row is kept if a ring slot with neighbors != -1 holds its id, if a node's s- or d-store run holds it, or if
+        its id is >= upto (default num_events).  Rows >= upto are kept verbatim whether referenced or not: that is how
+        a caller protects rows it has appended but not observed yet — pass upto = the first unobserved row; without it
+        such rows are retired like any other unreferenced row.
+
+        Afterwards num_events == n_live; the four table tensors and model.store are fresh allocations of `capacity`
+        rows (>= n_live, ValueError otherwise) or, by default, of grown_capacity's max(n_live + 1, 1.5 x n_live);
+        cfg.num_events, neg_train and out_ev follow the capacity (re-zeroed); loader.cur_e_id = n_live and
+        loader.version is bumped; ctl BATCH_START = CUR_EID = n_live, no other ctl word changes.  memory, last_update,
+        node_gen and the parameters are untouched; what the ring and the stores name is unchanged.  Like
+        reserve_events, everything that captured a pointer or names a row range is dropped — the captured train and
+        eval graphs, the plan table, and the resident train and eval bindings, which are NOT made again (their rows no
+        longer exist): bind again.  Train negatives drawn on the device after a compaction differ from an uncompacted
+        engine's (their RNG offset is the batch's CUR_EID).  The old and new tables coexist until this returns.
+
+        An event id outside [0, num_events) in the ring or a store is counted on the device, never dereferenced:
+        RuntimeError, with the engine untouched.  One device only (ValueError at world > 1).  One host read."""
+        upto = check_compact_args(self.num_events, upto, capacity, self.world)
+        if self.dp:
+            raise ValueError("compact_events: one device only (the data-parallel step forms are not built)")
+        self.finish()
+        self._prefetched = False
+        ws, n_live, n_arena, n_bad = self._compact_plan(upto)
+        if n_bad:
+            raise RuntimeError(f"compact_events: {n_bad} event ids / store runs outside the table's {self.num_events} "
+                               "rows in the ring or the message stores; nothing was changed")
+        if n_arena > 2 * n_live:
+            raise RuntimeError(f"compact_events: the stores hold {n_arena} entries for {n_live} live rows (an event "
+                               "twice in one run); nothing was changed")
+        cap = compact_capacity(n_live, capacity)
+        self._drop_bindings()
+        return self._compact_apply(ws, n_live, cap)
+
+    @torch.no_grad()
+    def stream_state(self) -> dict:
+        """The whole stream state as a flat dict of cloned tensors and plain ints (STREAM_STATE_KEYS): format = 1, the
+        fingerprint num_nodes / ring / mem_dim / msg_dim, num_events, the table rows [0, num_events), memory,
+        last_update, node_gen, the stores' node table and arena entries [0, 2 * num_events), the ring and the ctl
+        block.  No parameters: model.state_dict() has them.  Round-trips through torch.save / torch.load; small when
+        taken after compact_events(), valid without one."""
+        if self.world > 1:
+            raise ValueError("stream_state: one device only (world > 1 is not built)")
+        self.finish()
+        m, ld, N, n = self.model, self.loader, self.cfg.num_nodes, self.num_events
+        out = dict(format=STREAM_STATE_FORMAT, **stream_fingerprint(self.cfg), num_events=n)
+        tensors = dict(src=self.src, dst=self.dst, t=self.t, msg=self.msg, memory=m.memory.memory,
+                       last_update=m.memory.last_update, node_gen=m.node_gen, store_nodes=m.store[:4 * N].view(N, 4),
+                       store_arena=m.store[4 * N:4 * N + 2 * n], neighbors=ld.neighbors, e_id=ld.e_id, ring_t=ld.t,
+                       ctl=self.ctl)
+        out.update({k: tensors[k].detach().clone() for k in STREAM_STATE_TENSORS})
+        return out
+
+    @torch.no_grad()
+    def load_stream_state(self, state: dict) -> None:
+        """Make a stream_state() dict this engine's stream state, whatever table the engine was built over (one row
+        is enough).  format, the fingerprint, the shapes and ERR == 0 in the saved ctl are checked first: ValueError
+        before anything is written.  Table and store are sized by reserve_events, everything is copied in,
+        loader.cur_e_id = num_events, and bindings and graphs are dropped as compact_events drops them."""
+        if self.world > 1:
+            raise ValueError("load_stream_state: one device only (world > 1 is not built)")
+        n = check_stream_state(state, stream_fingerprint(self.cfg))
+        err = int(state["ctl"][11])
+        if err:
+            raise ValueError(f"load_stream_state: the saved ctl block carries step error flags {err:#x}")
+        self.finish()
+        self._drop_bindings()
+        self.reserve_events(max(n, 1))
+        torch.cuda.synchronize(self.dev)
+        for buf, k in zip(self._tab, ("src", "dst", "t", "msg")):
+            buf[:n].copy_(state[k].to(self.dev, buf.dtype))
+        self._set_rows(n)
+        m, ld, N = self.model, self.loader, self.cfg.num_nodes
+        m.store[:4 * N].copy_(state["store_nodes"].to(self.dev, torch.long).reshape(-1))
+        m.store[4 * N:4 * N + 2 * n].copy_(state["store_arena"].to(self.dev, torch.long))
+        for dst, k in ((m.memory.memory, "memory"), (m.memory.last_update, "last_update"), (m.node_gen, "node_gen"),
+                       (ld.neighbors, "neighbors"), (ld.e_id, "e_id"), (ld.t, "ring_t"), (self.ctl, "ctl")):
+            dst.copy_(state[k].to(self.dev, dst.dtype))
+        ld.cur_e_id = n
+        ld.version = getattr(ld, "version", 0) + 1
 
     # ------------------------------------------------------------------ read-only inference
     def embed_capacity(self) -> int:

@@ -21,6 +21,10 @@ updates the stores, the memory and the ring in eval order.
   observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
       table and taken into memory, stores and ring as test() batches would leave them, without negatives or scores
       (TgnEngine.observe_events)
+  compact(model, neighbor_loader, upto=None, capacity=None) -> kept: retire the event-table rows nothing references
+      and renumber the rest in order (TgnEngine.compact_events); kept[new] = old
+  save_stream(model, neighbor_loader, f) / load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
+      the whole stream state (table, memory, stores, ring, ctl; TgnEngine.stream_state) to / from a torch.save file
 
 Reached through pyg_epoch_utils (shim) and through epoch_utils.train / test, which dispatch here for a
 {'memory', 'gnn', 'link_pred'} model: the reference script runs with only its model import swapped
@@ -210,3 +214,59 @@ def observe(model, neighbor_loader, src, dst, t, msg, batch=None):
     start, n = eng.observe_events(src, dst, t, msg, batch=batch)
     neighbor_loader.cur_e_id = start + n
     return start, n
+
+
+def _bound_engine(model, neighbor_loader, what):
+    eng = getattr(_owner(model), "_tgnx_engine", None)
+    if eng is None or eng.loader is not neighbor_loader:
+        raise RuntimeError(f"tgnx {what}: no engine bound to this model / neighbor_loader yet (run train() or test() "
+                           "first: they bind the event table)")
+    return eng
+
+
+@torch.no_grad()
+def compact(model, neighbor_loader, upto=None, capacity=None):
+    """Retire every row of the resident event table that neither the ring nor a message store references and renumber
+    the survivors in order (TgnEngine.compact_events: rows >= upto are kept verbatim).  Returns kept, the surviving
+    rows' old ids (kept[new] = old).  The stream state is unchanged, so nothing is flushed; the train / eval bindings
+    and graphs of the loops above are dropped (their splits name rows that no longer exist): train() / test() over a
+    loader of the new numbering bind again."""
+    eng = _bound_engine(model, neighbor_loader, "compact")
+    kept = eng.compact_events(upto=upto, capacity=capacity)
+    neighbor_loader.cur_e_id = eng.num_events
+    return kept
+
+
+@torch.no_grad()
+def save_stream(model, neighbor_loader, f):
+    """torch.save the engine's stream state (TgnEngine.stream_state; no parameters: the model's state_dict() has them)
+    to the path or file object f.  Straight after train() the memory is switched to eval first, as test(), recommend()
+    and observe() do, so the file holds a serving state.  Small when taken after compact()."""
+    eng = _bound_engine(model, neighbor_loader, "save_stream")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    torch.save(eng.stream_state(), f)
+
+
+@torch.no_grad()
+def load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
+    """Load a save_stream file into the engine attached to the model — or, in a fresh process where none is, into a
+    new engine over a one-row table (optimizer and dst_nodes as train() would have given it) — and leave it in eval
+    mode: observe(), recommend() and test() go on from the saved state (TgnEngine.load_stream_state)."""
+    m = _owner(model)
+    eng = getattr(m, "_tgnx_engine", None)
+    state = torch.load(f, map_location="cpu")
+    if eng is None or eng.loader is not neighbor_loader:
+        d = m.cfg.msg_dim
+        eng = TgnEngine(m, neighbor_loader, dict(src=torch.zeros(1, dtype=torch.long), dst=torch.zeros(1, dtype=torch.long),
+                                                 t=torch.zeros(1), msg=torch.zeros(1, d)), optimizer,
+                        dst_nodes=None if dst_nodes is None else torch.as_tensor(dst_nodes))
+        eng.out_ev = torch.zeros(eng.cfg.num_events, 2, dtype=torch.float32, device=eng.dev)
+        eng.keep_grads = False
+        eng._bound = None
+        m._tgnx_engine = eng
+    eng.load_stream_state(state)
+    eng._mode_train = False
+    neighbor_loader.cur_e_id = eng.num_events
+    return eng.num_events
