@@ -17,6 +17,8 @@ for the 2B endpoint roots).
              within 2e-5 in the `_close` metric of test_gpu_tgn_query.py, last_update and ring exact;
   the stream goes on     both twins then run eval_batch on batch 6 with the same negatives: pos, neg, rr torch.equal,
              and embed() of the 120-node query set is equal;
+  tiny graph  40 nodes, B = max_batch = 32, one negative (N < 2B: the observe step's root capacity is N): DyRep and
+             2 hops, eval_batch against observe on batches 1-3, state torch.equal and the oracle's within 2e-5;
   append     an engine over the first 300 rows takes the other 300 in chunks of 50, 1, 137, 112 through
              observe_events(batch=50) — batching is per call, so the batches are [300,350) [350,351) [351,401) [401,451)
              [451,488) [488,538) [538,588) [588,600), which differ from a batching of [300, 600) by 50: the twin over
@@ -206,6 +208,67 @@ def test_the_stream_goes_on(form):
     nodes = _query_nodes(s, 7 * B)
     assert torch.equal(a.embed(nodes), b.embed(nodes))
     _assert_same_state(a, b, ctl=False)
+
+
+@pytest.mark.parametrize("form", ["dyrep_emb", "2hop_last"])
+def test_observe_on_a_graph_smaller_than_two_batches(form):
+    """N = 40 < 2B = 64 (max_batch = B = 32, one negative, 4 batches of the 128-event stream): the observe step's root
+    capacity is min(N, 2B) = N, as the eval step's min(N, B (2 + Kn)) is.  Batch 0 by eval_batch on both twins, then
+    batches 1-3 by eval_batch against observe: state torch.equal; and against the oracle's update_state within TOL."""
+    from oracle.sampler_ref import RefLastNeighborLoader
+    from oracle.tgn_ref import RefTGN, _emb_args, eval_step, sample_hops
+    from tgnx.sampler import LastNeighborLoader
+    from tgnx.synth import make_stream
+    from tgnx.tgn import TgnAdam, TgnEngine, TGNModel
+    n, b, nev = 40, 32, 128
+    s = make_stream("tgbl-wiki", seed=5, num_events=nev, num_nodes=n, msg_dim=d)
+    kw = dict(FORMS[form])
+    okw = {k: v for k, v in kw.items() if k != "memory"}
+    torch.manual_seed(0)
+    ref = RefTGN(n, d, hidden=D, dropout=0.0, **okw)
+    negs = torch.from_numpy(np.random.default_rng(9).choice(s.dst_nodes, size=(nev, 1)))
+    twins = []
+    for _ in range(2):
+        model = TGNModel(n, nev, d, D, DEV, ring=10, max_batch=b, max_neg=1, dropout=0.0, **kw)
+        model.load_reference_state(ref.state_dict())
+        e = TgnEngine(model, LastNeighborLoader(n, 10, device=DEV), _events(s, 0, nev), TgnAdam(model, 1e-3),
+                      dst_nodes=s.dst_nodes, seed=7)
+        e.reset_state()
+        e.flush()
+        _eval(e, negs, 0, 1, batch=b)
+        twins.append(e)
+    x, y = twins
+    assert n < 2 * b and int(y.cfg.max_batch) == b
+    _eval(x, negs, 1, 3, batch=b)
+    for st in range(1, 4):
+        y.observe(st * b, b)
+    torch.cuda.synchronize()
+    y.check()
+    _assert_same_state(x, y)
+    lref = RefLastNeighborLoader(n, 10)
+    ev_t, ev_msg = torch.from_numpy(s.t.astype(np.float32)), torch.from_numpy(s.msg)
+    src, dst = torch.from_numpy(s.src), torch.from_numpy(s.dst)
+    eval_step(ref, lref, ev_t, ev_msg, src[:b], dst[:b], negs[:b], ev_t[:b], ev_msg[:b])
+    ref.eval()
+    with torch.no_grad():
+        for st in range(1, 4):
+            sl = slice(st * b, (st + 1) * b)
+            emb = ()
+            if ref.memory.use_src_emb_in_msg or ref.memory.use_dst_emb_in_msg:
+                n_id, ei, e_id = sample_hops(ref, lref, torch.cat([src[sl], dst[sl]]).unique().numpy())
+                assoc = torch.zeros(n, dtype=torch.long)
+                assoc[n_id] = torch.arange(n_id.size(0))
+                z, lu = ref.memory(n_id)
+                z = ref.gnn(z, lu, ei, ev_t[e_id], ev_msg[e_id])
+                emb = _emb_args(ref, z, assoc)
+            ref.memory.update_state(src[sl], dst[sl], ev_t[sl], ev_msg[sl], *emb)
+            lref.insert(s.src[sl], s.dst[sl], s.t[sl].astype(np.float32))
+    sy = _state(y)
+    _close(sy["memory"], ref.memory.memory, TOL)
+    assert torch.equal(sy["last_update"].cpu(), ref.memory.last_update)
+    assert np.array_equal(sy["neighbors"].cpu().numpy(), lref.neighbors)
+    assert np.array_equal(sy["e_id"].cpu().numpy(), lref.e_id)
+    assert np.array_equal(sy["t"].cpu().numpy(), lref.t.astype(np.float32))
 
 
 CHUNKS = (50, 1, 137, 112)

@@ -5408,11 +5408,26 @@ static bool pred_smem_ok(int D) {
   return ok && tgn_pred_smem(D) <= tgn_pred_smem(TDMAX);
 }
 
-struct AdvArgs {
+// the device batch cursor's arguments: the split's event rows [lo, hi), the global batch, this rank of world, the seed
+struct Cursor {
   int64_t lo, hi, batch;
   int rank, world;
   uint64_t seed;
 };
+static bool cursor_ok(const Cursor& a, const tgnx_tgn_config* cfg, const Ctx& c) {
+  return a.batch > 0 && a.batch <= cfg->max_batch && a.world >= 1 && a.rank >= 0 && a.rank < a.world && a.lo >= 0 &&
+         a.hi >= a.lo && a.hi <= c.nev;
+}
+static void set_cursor(Ctx& c, const Cursor& a) {
+  c.adv = 1;
+  c.adv_lo = a.lo;
+  c.adv_hi = a.hi;
+  c.adv_batch = a.batch;
+  c.adv_rank = a.rank;
+  c.adv_world = a.world;
+  c.adv_seed = a.seed;
+}
+static void train_scan(hipStream_t s, const Ctx& c, const Caps& k);  // (below, beside tgnx_tgn_scan_next)
 // pipe (resident world-1 fused steps only): 0 = plain step; 1 = pipelined, this batch already marked and
 // scanned by the previous pipelined step; 2 = pipelined, mark + scan this batch first.  A pipelined step
 // marks the next batch inside tgn_pred_train and scans it after its own last launch.
@@ -5431,7 +5446,7 @@ static inline bool scan_folds(const Ctx& c, const Caps& k, const Caps& kr) {
 // written while this step's later launches still read set pp's), the fixup launch only writes its descriptor
 template <int CELL>
 static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t gen_neg, int32_t dropout,
-                             void* stream, bool fuse_adam, const AdvArgs* adv, int pipe, int pp) {
+                             void* stream, bool fuse_adam, const Cursor* adv, int pipe, int pp) {
   using Cl = CellOps<CELL>;
   const bool no_tail = (pipe & 4) != 0;  // pipelined, but the next batch's scan is the caller's (tgnx_tgn_scan_next)
   pipe &= 3;
@@ -5441,21 +5456,14 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
   int rc = make_ctx(cfg, buf, 1, c, k, W);
   if (rc) return rc;
   if (adv) {
-    TGNX_CHECK_ARG(adv->batch > 0 && adv->batch <= cfg->max_batch && adv->world >= 1 && adv->rank >= 0 &&
-                       adv->rank < adv->world && adv->lo >= 0 && adv->hi >= adv->lo && adv->hi <= c.nev,
+    TGNX_CHECK_ARG(cursor_ok(*adv, cfg, c),
                    "tgnx_tgn_train_step_resident: bad cursor arguments (batch, rank / world, or split beyond the "
                    "event table)");
     // the fused step applies Adam to this rank's gradients in place: only a world-1 step has the whole sum
     TGNX_CHECK_ARG(!fuse_adam || adv->world == 1,
                    "tgnx_tgn_train_step_resident: world > 1 steps all-reduce before Adam "
                    "(tgnx_tgn_train_fwd_bwd_resident + exchange + tgnx_tgn_train_update)");
-    c.adv = 1;
-    c.adv_lo = adv->lo;
-    c.adv_hi = adv->hi;
-    c.adv_batch = adv->batch;
-    c.adv_rank = adv->rank;
-    c.adv_world = adv->world;
-    c.adv_seed = adv->seed;
+    set_cursor(c, *adv);
   }
   // data parallel: the rank's share ceil(B / world) of the global batch sets every per-rank capacity that
   // sizes a grid or a GEMM shape (roots, sampled nodes / edges, predictor rows, update list): grids sized
@@ -5526,9 +5534,7 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
     const int nmark = gridn(3 * kr.B * 16, 256);
     tgn_mark<true><<<nmark, 256, 0, s>>>(c, nmark);
     TGNX_LAUNCH_CHECK("tgn_mark");
-    probe_begin(TGNX_K_ASSEMBLE, s);
-    tgn_scan<true><<<1 + 2 * c.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B), s>>>(c, 0, 1);
-    probe_end(TGNX_K_ASSEMBLE, s);
+    train_scan(s, c, k);
     TGNX_LAUNCH_CHECK("tgn_scan");
   }
   const int nedge = gridn((int64_t)kr.Rtr * c.K, 4, TGNX_AGG_EDGE_CAP);
@@ -5800,9 +5806,7 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
   probe_end(TGNX_K_FINISH, s);
   TGNX_LAUNCH_CHECK("tgn_fixup_update");
   if (scan_next && !fold) {  // the next batch (counters advanced by SnapJob): sorted node sets, plans, descriptor
-    probe_begin(TGNX_K_ASSEMBLE, s);
-    tgn_scan<true><<<1 + 2 * c.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B), s>>>(c, 0, 1);
-    probe_end(TGNX_K_ASSEMBLE, s);
+    train_scan(s, c, k);
     TGNX_LAUNCH_CHECK("tgn_scan_next");
   }
   return TGNX_OK;
@@ -5811,7 +5815,7 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
 }  // extern "C++"
 
 static int train_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t gen_neg, int32_t dropout,
-                           void* stream, bool fuse_adam, const AdvArgs* adv = nullptr, int pipe = 0, int pp = -1) {
+                           void* stream, bool fuse_adam, const Cursor* adv = nullptr, int pipe = 0, int pp = -1) {
   if (cfg && cfg->updater == 1) return train_step_impl_c<1>(cfg, buf, gen_neg, dropout, stream, fuse_adam, adv, pipe, pp);
   return train_step_impl_c<0>(cfg, buf, gen_neg, dropout, stream, fuse_adam, adv, pipe, pp);
 }
@@ -5829,21 +5833,21 @@ int tgnx_tgn_train_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf,
 int tgnx_tgn_train_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                  int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                  int32_t dropout, void* stream) {
-  const AdvArgs a{split_lo, split_hi, batch, rank, world, base_seed};
+  const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
   return train_step_impl(cfg, buf, 1, dropout, stream, true, &a);
 }
 
 int tgnx_tgn_train_step_pipelined(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                   int64_t split_hi, int64_t batch, uint64_t base_seed, int32_t dropout,
                                   int32_t prefetched, void* stream) {
-  const AdvArgs a{split_lo, split_hi, batch, 0, 1, base_seed};
+  const Cursor a{split_lo, split_hi, batch, 0, 1, base_seed};
   return train_step_impl(cfg, buf, 1, dropout, stream, true, &a, prefetched ? 1 : 2);
 }
 
 int tgnx_tgn_train_step_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo, int64_t split_hi,
                            int64_t batch, uint64_t base_seed, int32_t dropout, int32_t prefetched, int32_t parity,
                            void* stream) {
-  const AdvArgs a{split_lo, split_hi, batch, 0, 1, base_seed};
+  const Cursor a{split_lo, split_hi, batch, 0, 1, base_seed};
   TGNX_CHECK_ARG(parity == 0 || parity == 1, "tgnx_tgn_train_step_pp: parity must be 0 or 1");
   return train_step_impl(cfg, buf, 1, dropout, stream, true, &a, prefetched ? 1 : 2, parity);
 }
@@ -5858,17 +5862,23 @@ int tgnx_tgn_train_fwd_bwd_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers
     const int rc = tgnx_tgn_apply_rows_update(cfg, buf, rows, nrows, stream);
     if (rc) return rc;
   }
-  const AdvArgs a{split_lo, split_hi, batch, rank, world, base_seed};
+  const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
   return train_step_impl(cfg, buf, 1, dropout, stream, false, &a, prefetched ? 1 : 2, parity);
 }
 
 int tgnx_tgn_train_fwd_bwd_split(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                  int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                  int32_t dropout, int32_t prefetched, void* stream) {
-  const AdvArgs a{split_lo, split_hi, batch, rank, world, base_seed};
+  const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
   return train_step_impl(cfg, buf, 1, dropout, stream, false, &a, (prefetched ? 1 : 2) | 4);
 }
 
+// the train step's scan of a batch (sorted node sets, plans, descriptor); the caller checks the launch under its label
+static void train_scan(hipStream_t s, const Ctx& c, const Caps& k) {
+  probe_begin(TGNX_K_ASSEMBLE, s);
+  tgn_scan<true><<<1 + 2 * c.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B), s>>>(c, 0, 1);
+  probe_end(TGNX_K_ASSEMBLE, s);
+}
 int tgnx_tgn_scan_next(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo, int64_t split_hi,
                        int64_t batch, int32_t rank, int32_t world, uint64_t base_seed, void* stream) {
   Ctx c;
@@ -5876,20 +5886,10 @@ int tgnx_tgn_scan_next(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
   WsLay W;
   int rc = make_ctx(cfg, buf, 1, c, k, W);
   if (rc) return rc;
-  TGNX_CHECK_ARG(batch > 0 && batch <= cfg->max_batch && world >= 1 && rank >= 0 && rank < world && split_lo >= 0 &&
-                     split_hi >= split_lo && split_hi <= c.nev,
-                 "tgnx_tgn_scan_next: bad cursor arguments");
-  c.adv = 1;
-  c.adv_lo = split_lo;
-  c.adv_hi = split_hi;
-  c.adv_batch = batch;
-  c.adv_rank = rank;
-  c.adv_world = world;
-  c.adv_seed = base_seed;
-  hipStream_t s = as_stream(stream);
-  probe_begin(TGNX_K_ASSEMBLE, s);
-  tgn_scan<true><<<1 + 2 * c.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B), s>>>(c, 0, 1);
-  probe_end(TGNX_K_ASSEMBLE, s);
+  const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
+  TGNX_CHECK_ARG(cursor_ok(a, cfg, c), "tgnx_tgn_scan_next: bad cursor arguments");
+  set_cursor(c, a);
+  train_scan(as_stream(stream), c, k);
   TGNX_LAUNCH_CHECK("tgn_scan_next");
   return TGNX_OK;
 }
@@ -5897,14 +5897,14 @@ int tgnx_tgn_scan_next(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
 int tgnx_tgn_train_fwd_bwd_pipelined(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                      int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                      int32_t dropout, int32_t prefetched, void* stream) {
-  const AdvArgs a{split_lo, split_hi, batch, rank, world, base_seed};
+  const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
   return train_step_impl(cfg, buf, 1, dropout, stream, false, &a, prefetched ? 1 : 2);
 }
 
 int tgnx_tgn_train_fwd_bwd_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                     int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                     int32_t dropout, void* stream) {
-  const AdvArgs a{split_lo, split_hi, batch, rank, world, base_seed};
+  const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
   return train_step_impl(cfg, buf, 1, dropout, stream, false, &a);
 }
 
@@ -5954,50 +5954,25 @@ int tgnx_tgn_apply_rows_update(const tgnx_tgn_config* cfg, const tgnx_tgn_buffer
 // res (tgnx_tgn_eval_step_resident): the batch from the device cursor, the deduplicated marking, and the batch's
 // reciprocal ranks copied to their event rows; everything between is tgnx_tgn_eval_step's launch sequence
 struct EvalRes {
-  int64_t lo, hi, batch;
-  int rank, world;
-  uint64_t seed;
+  Cursor cur;
   double* rr_ev;
 };
-static int eval_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t Kn, void* stream,
-                          const EvalRes* res) {
-  Ctx c;
-  Caps k;
-  WsLay W;
-  TGNX_CHECK_ARG(cfg && Kn >= 1 && Kn <= (cfg->max_neg < 1 ? 1 : cfg->max_neg), "tgnx_tgn_eval_step: Kn out of range");
-  int rc = make_ctx(cfg, buf, Kn, c, k, W);
-  if (rc) return rc;
-  TGNX_CHECK_ARG(buf->neg && buf->out_pos && buf->out_neg && buf->mrr, "tgnx_tgn_eval_step: null buffer");
-  hipStream_t s = as_stream(stream);
-  if (res) {
-    TGNX_CHECK_ARG(res->rr_ev && res->batch > 0 && res->batch <= cfg->max_batch && res->world >= 1 && res->rank >= 0 &&
-                       res->rank < res->world && res->lo >= 0 && res->hi >= res->lo && res->hi <= c.nev,
-                   "tgnx_tgn_eval_step_resident: bad cursor arguments (rr_ev, batch, rank / world, or split beyond "
-                   "the event table)");
-    // buf->neg is the split's table: the kernels index it by absolute event row
-    c.neg = buf->neg - res->lo * (int64_t)Kn;
-    tgn_eval_cursor<<<1, 64, 0, s>>>(c.ctl, c.cnt, res->lo, res->hi, res->batch, res->rank, res->world, res->seed);
-    TGNX_LAUNCH_CHECK("tgn_eval_cursor");
-  }
+// the eval marking of a batch's roots (src, dst, Kn negatives per event) and their ring rows; the caller checks the launch
+static void mark_roots(hipStream_t s, const Ctx& c, const Caps& k, int Kn) {
+  const int nmark = gridn((int64_t)k.B * (2 + Kn) * 16, 256);
+  tgn_mark<false><<<nmark, 256, 0, s>>>(c, nmark);
+}
+// the inference forward of the marked roots (eval step, embed, observe with DyRep embedding messages): scan,
+// Δt encodings, lin_edge ‖ projections, attention; 2 hops: conv2 over the roots.  R1q: the caller's root capacity;
+// scan_blocks: role 0, + the 2 pplan plan roles of a batch's events; cr: the root-level view (1 hop: c itself)
+static int infer_forward(hipStream_t s, const Ctx& c, const Caps& k, int R1q, int scan_blocks, Ctx& cr) {
   const float* P = c.params;
   const int D = c.D, HC = c.HC, d = c.d;
   const bool two = k.layers == 2;
-  const int R1q = (int)std::min<int64_t>(c.N, (int64_t)k.B * (2 + Kn));  // roots
   const int Rq = two ? (int)std::min<int64_t>(c.N, (int64_t)R1q * (c.K + 1)) : R1q;  // (outer) centres
   const int Mq = (int)std::min<int64_t>(c.N, (int64_t)Rq * (c.K + 1));
   const int Eq = Rq * c.K, E1q = two ? R1q * c.K : 0;
-  if (res) {
-    int* own = reinterpret_cast<int*>(reinterpret_cast<char*>(buf->ws) + W.own);
-    const int nslot = gridn((int64_t)k.B * (2 + Kn), 256, 4096);
-    tgn_eval_claim<<<nslot, 256, 0, s>>>(c, own);
-    TGNX_LAUNCH_CHECK("tgn_eval_claim");
-    tgn_mark_eval<<<nslot, 256, 0, s>>>(c, own);
-  } else {
-    const int nmark = gridn((int64_t)k.B * (2 + Kn) * 16, 256);
-    tgn_mark<false><<<nmark, 256, 0, s>>>(c, nmark);
-  }
-  TGNX_LAUNCH_CHECK("tgn_mark");
-  tgn_scan<false><<<1 + 2 * c.pplan, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
+  tgn_scan<false><<<scan_blocks, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
   TGNX_LAUNCH_CHECK("tgn_scan");
   const int nedge = gridn((int64_t)Rq * c.K, 4, 4096);
   tgn_agg_emit<-1><<<nedge + gridn(Mq, 256), 256, 0, s>>>(c, 1, nedge, nullptr, nullptr, 0, 0);
@@ -6018,7 +5993,7 @@ static int eval_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* bu
   TGNX_LAUNCH_CHECK("tgn_edge_proj");
   tgn_attn_fwd<false><<<gridn(Rq, 4, 1 << 20), 256, 0, s>>>(c);
   TGNX_LAUNCH_CHECK("tgn_attn_fwd");
-  const Ctx cr = two ? root_view(c) : c;
+  cr = two ? root_view(c) : c;
   if (two) {
     gemm_launch<G32>(gemm_shape<G32>(Rq, 4 * HC, HC, c.cnt + CNT_R), LoadRowK{c.Zc, Rq, HC, HC},
                      LoadProjW{P + c.L.wq2, c.L.pw, HC, HC}, EpiProj{P + c.L.bq2, c.L.pb, c.P2, HC}, nullptr, s);
@@ -6026,14 +6001,10 @@ static int eval_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* bu
     tgn_attn_fwd<false><<<gridn(R1q, 4, 1 << 20), 256, 0, s>>>(cr);
     TGNX_LAUNCH_CHECK("tgn_attn_fwd2");
   }
-  gemm2_launch<G32, G32>(gemm_shape<G32>(R1q, D, D, c.cnt + cr.rsel), LoadRowK{cr.Zc, R1q, D, D},
-               LoadRowK{P + c.L.lsw, D, D, D}, EpiStore{c.Hs, P + c.L.lsb, D, 0}, nullptr,
-               gemm_shape<G32>(R1q, D, D, c.cnt + cr.rsel), LoadRowK{cr.Zc, R1q, D, D}, LoadRowK{P + c.L.ldw, D, D, D},
-               EpiStore{c.Hd, P + c.L.ldb, D, 0}, nullptr, s);
-  TGNX_LAUNCH_CHECK("tgn_lin_src_dst");
-  tgn_score<<<k.B, 256, 0, s>>>(cr);
-  TGNX_LAUNCH_CHECK("tgn_score");
-  // update_state in eval order: stores first, then the GRU of src ∪ dst; ring insert
+  return TGNX_OK;
+}
+// update_state in eval order: stores first (‖ the ring insert), then the GRU of src ∪ dst, then the memory write
+static int eval_update(hipStream_t s, const Ctx& c, const Caps& k) {
   const int nst = gridn(2 * k.B, 256), nring = gridn(2 * k.B, 4);
   tgn_update<<<nst + nring, 256, 0, s>>>(c, 0, nst, 1, nullptr, nullptr, 0, 0);
   TGNX_LAUNCH_CHECK("tgn_store_insert");
@@ -6042,8 +6013,53 @@ static int eval_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* bu
   TGNX_LAUNCH_CHECK("tgn_gru_update");
   tgn_update<<<gridn(k.Ucap, 4, 1024), 256, 0, s>>>(c, gridn(k.Ucap, 4, 1024), 0, 1, c.upd, c.cnt + CNT_U, 0, 0);
   TGNX_LAUNCH_CHECK("tgn_memory_write");
+  return TGNX_OK;
+}
+static int eval_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t Kn, void* stream,
+                          const EvalRes* res) {
+  Ctx c;
+  Caps k;
+  WsLay W;
+  TGNX_CHECK_ARG(cfg && Kn >= 1 && Kn <= (cfg->max_neg < 1 ? 1 : cfg->max_neg), "tgnx_tgn_eval_step: Kn out of range");
+  int rc = make_ctx(cfg, buf, Kn, c, k, W);
+  if (rc) return rc;
+  TGNX_CHECK_ARG(buf->neg && buf->out_pos && buf->out_neg && buf->mrr, "tgnx_tgn_eval_step: null buffer");
+  hipStream_t s = as_stream(stream);
   if (res) {
-    tgn_eval_rr<<<gridn(k.B, 256), 256, 0, s>>>(c.ctl, c.mrr, res->rr_ev, res->lo);
+    const Cursor& a = res->cur;
+    TGNX_CHECK_ARG(res->rr_ev && cursor_ok(a, cfg, c),
+                   "tgnx_tgn_eval_step_resident: bad cursor arguments (rr_ev, batch, rank / world, or split beyond "
+                   "the event table)");
+    // buf->neg is the split's table: the kernels index it by absolute event row
+    c.neg = buf->neg - a.lo * (int64_t)Kn;
+    tgn_eval_cursor<<<1, 64, 0, s>>>(c.ctl, c.cnt, a.lo, a.hi, a.batch, a.rank, a.world, a.seed);
+    TGNX_LAUNCH_CHECK("tgn_eval_cursor");
+  }
+  const float* P = c.params;
+  const int D = c.D;
+  const int R1q = (int)std::min<int64_t>(c.N, (int64_t)k.B * (2 + Kn));  // roots
+  if (res) {
+    int* own = reinterpret_cast<int*>(reinterpret_cast<char*>(buf->ws) + W.own);
+    const int nslot = gridn((int64_t)k.B * (2 + Kn), 256, 4096);
+    tgn_eval_claim<<<nslot, 256, 0, s>>>(c, own);
+    TGNX_LAUNCH_CHECK("tgn_eval_claim");
+    tgn_mark_eval<<<nslot, 256, 0, s>>>(c, own);
+  } else {
+    mark_roots(s, c, k, Kn);
+  }
+  TGNX_LAUNCH_CHECK("tgn_mark");
+  Ctx cr;
+  if ((rc = infer_forward(s, c, k, R1q, 1 + 2 * c.pplan, cr))) return rc;
+  gemm2_launch<G32, G32>(gemm_shape<G32>(R1q, D, D, c.cnt + cr.rsel), LoadRowK{cr.Zc, R1q, D, D},
+               LoadRowK{P + c.L.lsw, D, D, D}, EpiStore{c.Hs, P + c.L.lsb, D, 0}, nullptr,
+               gemm_shape<G32>(R1q, D, D, c.cnt + cr.rsel), LoadRowK{cr.Zc, R1q, D, D}, LoadRowK{P + c.L.ldw, D, D, D},
+               EpiStore{c.Hd, P + c.L.ldb, D, 0}, nullptr, s);
+  TGNX_LAUNCH_CHECK("tgn_lin_src_dst");
+  tgn_score<<<k.B, 256, 0, s>>>(cr);
+  TGNX_LAUNCH_CHECK("tgn_score");
+  if ((rc = eval_update(s, c, k))) return rc;
+  if (res) {
+    tgn_eval_rr<<<gridn(k.B, 256), 256, 0, s>>>(c.ctl, c.mrr, res->rr_ev, res->cur.lo);
     TGNX_LAUNCH_CHECK("tgn_eval_rr");
   }
   return TGNX_OK;
@@ -6054,11 +6070,11 @@ int tgnx_tgn_eval_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
 int tgnx_tgn_eval_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                 int64_t split_hi, int64_t batch, int32_t Kn, int32_t rank, int32_t world,
                                 uint64_t base_seed, double* rr_ev, void* stream) {
-  const EvalRes r{split_lo, split_hi, batch, rank, world, base_seed, rr_ev};
+  const EvalRes r{{split_lo, split_hi, batch, rank, world, base_seed}, rr_ev};
   return eval_step_impl(cfg, buf, Kn, stream, &r);
 }
 
-// eval_step_impl's launches up to the embedding, for the roots nodes[n]; see tgn_embed_claim
+// the eval step's forward (infer_forward) up to the embedding, for the roots nodes[n]; see tgn_embed_claim
 int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg) {
   if (check_cfg(cfg)) return 0;
   return make_caps(cfg).R1cap;
@@ -6081,48 +6097,15 @@ int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, cons
   int64_t* live = c.ctl;
   c.ctl = reinterpret_cast<int64_t*>(ws + W.qctl);
   c.errw = c.ctl + TGNX_CTL_ERR;
-  const float* P = c.params;
-  const int D = c.D, HC = c.HC, d = c.d, nn = (int)n;
-  const bool two = k.layers == 2;
-  const int R1q = k.R1cap;                                                               // roots
-  const int Rq = two ? (int)std::min<int64_t>(c.N, (int64_t)R1q * (c.K + 1)) : R1q;  // (outer) centres
-  const int Mq = (int)std::min<int64_t>(c.N, (int64_t)Rq * (c.K + 1));
-  const int Eq = Rq * c.K, E1q = two ? R1q * c.K : 0;
+  const int nn = (int)n;
   const int nslot = gridn(n, 256, 4096);
   tgn_embed_claim<<<nslot, 256, 0, s>>>(c, live, own, nodes, nn, n_invalid);
   TGNX_LAUNCH_CHECK("tgn_embed_claim");
   tgn_embed_mark<<<nslot, 256, 0, s>>>(c, own, nodes, nn);
   TGNX_LAUNCH_CHECK("tgn_embed_mark");
   // role 0 alone: roles >= 1 build the insert / store plans of a batch's events, and there is no batch
-  tgn_scan<false><<<1, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
-  TGNX_LAUNCH_CHECK("tgn_scan");
-  const int nedge = gridn((int64_t)Rq * c.K, 4, 4096);
-  tgn_agg_emit<-1><<<nedge + gridn(Mq, 256), 256, 0, s>>>(c, 1, nedge, nullptr, nullptr, 0, 0);
-  TGNX_LAUNCH_CHECK("tgn_emit");
-  const LoadEdgeAttr ea{c.encE, c.e_id, c.ev_msg, D, d};
-  const auto j_edge = gemm_job<G32>(gemm_shape<G32>(Eq, HC, D + d, c.cnt + CNT_E), ea,
-                                    LoadRowK{P + c.L.we, HC, D + d, D + d}, EpiStore{c.Ep, nullptr, HC, 0}, (float*)nullptr);
-  const auto j_proj = gemm_job<G32>(gemm_shape<G32>(Mq, 4 * HC, D, c.cnt + CNT_M), LoadZ{c.Z0, c.mem, c.nid, D, 1},
-                                    LoadProjW{P + c.L.wq, c.L.pw, HC, D}, EpiProj{P + c.L.bq, c.L.pb, c.P, HC},
-                                    (float*)nullptr);
-  if (two)
-    gemmN_launch(s, j_edge, j_proj,
-                 gemm_job<G32>(gemm_shape<G32>(E1q, HC, D + d, c.cnt + CNT_E1),
-                               LoadEdgeAttrMap{c.encE, c.e1_id, c.e1_e2, c.ev_msg, D, d},
-                               LoadRowK{P + c.L.we2, HC, D + d, D + d}, EpiStore{c.Ep2, nullptr, HC, 0}, (float*)nullptr));
-  else
-    gemmN_launch(s, j_edge, j_proj);
-  TGNX_LAUNCH_CHECK("tgn_edge_proj");
-  tgn_attn_fwd<false><<<gridn(Rq, 4, 1 << 20), 256, 0, s>>>(c);
-  TGNX_LAUNCH_CHECK("tgn_attn_fwd");
-  const Ctx cr = two ? root_view(c) : c;
-  if (two) {
-    gemm_launch<G32>(gemm_shape<G32>(Rq, 4 * HC, HC, c.cnt + CNT_R), LoadRowK{c.Zc, Rq, HC, HC},
-                     LoadProjW{P + c.L.wq2, c.L.pw, HC, HC}, EpiProj{P + c.L.bq2, c.L.pb, c.P2, HC}, nullptr, s);
-    TGNX_LAUNCH_CHECK("tgn_proj2");
-    tgn_attn_fwd<false><<<gridn(R1q, 4, 1 << 20), 256, 0, s>>>(cr);
-    TGNX_LAUNCH_CHECK("tgn_attn_fwd2");
-  }
+  Ctx cr;
+  if ((rc = infer_forward(s, c, k, k.R1cap, 1, cr))) return rc;
   tgn_embed_gather<<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
   TGNX_LAUNCH_CHECK("tgn_embed_gather");
   return TGNX_OK;
@@ -6143,41 +6126,16 @@ int tgnx_tgn_observe_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* bu
     // DyRep embedding messages (1 hop): the stored messages carry the eval forward's embeddings of src ∪ dst, so the
     // forward runs for the 2B endpoint roots — the eval marking with no negative slots adds their ring rows to the
     // endpoints marked above — up to the attention; no predictor, no score
-    const float* P = c.params;
-    const int D = c.D, HC = c.HC, d = c.d;
-    const int Rq = (int)std::min<int64_t>(c.N, 2 * (int64_t)k.B);
-    const int Mq = (int)std::min<int64_t>(c.N, (int64_t)Rq * (c.K + 1));
-    const int Eq = Rq * c.K;
-    const int nmark = gridn((int64_t)k.B * 2 * 16, 256);
-    tgn_mark<false><<<nmark, 256, 0, s>>>(c, nmark);
+    // (check_cfg admits emb_in_msg at layers = 1 only: infer_forward's 2-hop branch is not taken here)
+    mark_roots(s, c, k, 0);
     TGNX_LAUNCH_CHECK("tgn_mark");
-    tgn_scan<false><<<1 + 2 * c.pplan, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
-    TGNX_LAUNCH_CHECK("tgn_scan");
-    const int nedge = gridn((int64_t)Rq * c.K, 4, 4096);
-    tgn_agg_emit<-1><<<nedge + gridn(Mq, 256), 256, 0, s>>>(c, 1, nedge, nullptr, nullptr, 0, 0);
-    TGNX_LAUNCH_CHECK("tgn_emit");
-    gemmN_launch(s,
-                 gemm_job<G32>(gemm_shape<G32>(Eq, HC, D + d, c.cnt + CNT_E), LoadEdgeAttr{c.encE, c.e_id, c.ev_msg, D, d},
-                               LoadRowK{P + c.L.we, HC, D + d, D + d}, EpiStore{c.Ep, nullptr, HC, 0}, (float*)nullptr),
-                 gemm_job<G32>(gemm_shape<G32>(Mq, 4 * HC, D, c.cnt + CNT_M), LoadZ{c.Z0, c.mem, c.nid, D, 1},
-                               LoadProjW{P + c.L.wq, c.L.pw, HC, D}, EpiProj{P + c.L.bq, c.L.pb, c.P, HC},
-                               (float*)nullptr));
-    TGNX_LAUNCH_CHECK("tgn_edge_proj");
-    tgn_attn_fwd<false><<<gridn(Rq, 4, 1 << 20), 256, 0, s>>>(c);
-    TGNX_LAUNCH_CHECK("tgn_attn_fwd");
+    Ctx cr;
+    if ((rc = infer_forward(s, c, k, (int)std::min<int64_t>(c.N, 2 * (int64_t)k.B), 1 + 2 * c.pplan, cr))) return rc;
   } else {
     tgn_scan<false><<<1 + 2 * c.pplan, TGN_SCAN_THREADS, tgn_scan_smem(k.B), s>>>(c, 0, 1);
     TGNX_LAUNCH_CHECK("tgn_scan");
   }
-  // update_state in eval order and the ring insert: eval_step_impl's last three calls
-  const int nst = gridn(2 * k.B, 256), nring = gridn(2 * k.B, 4);
-  tgn_update<<<nst + nring, 256, 0, s>>>(c, 0, nst, 1, nullptr, nullptr, 0, 0);
-  TGNX_LAUNCH_CHECK("tgn_store_insert");
-  gru_list(c, k, c.upd, c.cnt + CNT_U, 0, 0, k.Ucap, s, c.emb != 0);
-  TGNX_LAUNCH_CHECK("tgn_gru_update");
-  tgn_update<<<gridn(k.Ucap, 4, 1024), 256, 0, s>>>(c, gridn(k.Ucap, 4, 1024), 0, 1, c.upd, c.cnt + CNT_U, 0, 0);
-  TGNX_LAUNCH_CHECK("tgn_memory_write");
-  return TGNX_OK;
+  return eval_update(s, c, k);
 }
 
 size_t tgnx_tgn_flush_scratch_bytes(const tgnx_tgn_config* cfg) {

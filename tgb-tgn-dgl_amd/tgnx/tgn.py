@@ -591,25 +591,28 @@ class TgnEngine:
         """The next resident step marks, scans and gathers its batch itself (model.invalidate_prefetch)."""
         self._prefetched = False
 
-    def advance(self, batch_start: int, B: int, train: bool):
+    def _settle(self):
+        """Every call that reads or rewrites the state runs this first: a deferred data-parallel apply lands now, and
+        the next train step prepares its batch itself."""
         self.finish()
         self._prefetched = False
+
+    def advance(self, batch_start: int, B: int, train: bool):
+        self._settle()
         _lib.call("tgnx_tgnn_advance", _p(self.ctl), 0, batch_start, B, batch_start, 0, 0, 1, self.rank, self.world,
                   self.seed, 1 if train else 0, self._stream())
 
     # ------------------------------------------------------------------ state
     def reset_state(self):
         """memory_module.reset_state + neighbor_loader.reset_state (pyg_epoch_utils.py:15-16)."""
-        self.finish()
-        self._prefetched = False
+        self._settle()
         b = self._buffers(0)
         _lib.call("tgnx_tgn_reset_state", ctypes.byref(self.cfg), ctypes.byref(b), self._stream())
         self.loader.reset_state()
 
     def flush(self):
         """TGNMemory.train(False) (memory_module.py:209-215)."""
-        self.finish()
-        self._prefetched = False
+        self._settle()
         b = self._buffers(0)
         nb = int(_lib.lib().tgnx_tgn_flush_scratch_bytes(ctypes.byref(self.cfg)))
         # graphs beyond one workspace chunk: a snapshot of memory / last_update.  It is allocated on, and
@@ -740,8 +743,7 @@ class TgnEngine:
         start = self.num_events
         if n == 0:
             return start, 0
-        self.finish()
-        self._prefetched = False
+        self._settle()
         self.reserve_events(grown_capacity(self.event_capacity, start + n))
         for buf, rows in zip(self._tab, (src, dst, t, msg)):
             buf[start:start + n].copy_(rows)
@@ -866,8 +868,7 @@ class TgnEngine:
         upto = check_compact_args(self.num_events, upto, capacity, self.world)
         if self.dp:
             raise ValueError("compact_events: one device only (the data-parallel step forms are not built)")
-        self.finish()
-        self._prefetched = False
+        self._settle()
         ws, n_live, n_arena, n_bad = self._compact_plan(upto)
         if n_bad:
             raise RuntimeError(f"compact_events: {n_bad} event ids / store runs outside the table's {self.num_events} "
@@ -942,8 +943,7 @@ class TgnEngine:
         messages of the last batches are not in the memory rows read here.  Node sets beyond embed_capacity() run in
         chunks.  validate: one host read checks the ids against [0, N) and raises ValueError; without it an id out
         of range gets a zero row."""
-        self.finish()
-        self._prefetched = False
+        self._settle()
         nodes = torch.as_tensor(nodes).to(self.dev, torch.long).contiguous().view(-1)
         n, N = nodes.numel(), self.cfg.num_nodes
         if validate and n and bool(((nodes < 0) | (nodes >= N)).any()):
@@ -1000,8 +1000,7 @@ class TgnEngine:
         if not (0 <= lo <= hi <= self.src.numel()) or not (0 < batch <= self.cfg.max_batch):
             raise ValueError(f"bind_eval_resident: split [{lo}, {hi}) batch {batch} outside the event table "
                              f"({self.src.numel()} events) / max_batch ({self.cfg.max_batch})")
-        self.finish()
-        self._prefetched = False
+        self._settle()
         Kn = int(negs.shape[1])
         self.ensure_neg(Kn)
         self._ev = (lo, hi, batch, Kn)
@@ -1020,25 +1019,20 @@ class TgnEngine:
     def begin_eval(self):
         """Rewind the eval cursor to split_lo (the start of a pass).  Like every non-train call it settles a deferred
         data-parallel apply and makes the next train step prepare its batch again."""
-        self.finish()
-        self._prefetched = False
+        self._settle()
         self.ctl[18] = 0
 
     def _eval_step(self):
         if self._ev is None:
             raise RuntimeError("TgnEngine: no eval pass bound (bind_eval_resident)")
         lo, hi, batch, Kn = self._ev
-        rc = _lib.lib().tgnx_tgn_eval_step_resident(ctypes.byref(self.cfg), self._ev_buf_ref, lo, hi, batch, Kn, self.rank,
-                                                    self.world, self.seed, ctypes.c_void_p(self._ev_rr.data_ptr()),
-                                                    self._stream())
-        if rc:
-            raise RuntimeError(f"tgnx_tgn_eval_step_resident failed: {_lib.lib().tgnx_last_error().decode()}")
+        _lib.call("tgnx_tgn_eval_step_resident", ctypes.byref(self.cfg), self._ev_buf_ref, lo, hi, batch, Kn, self.rank,
+                  self.world, self.seed, ctypes.c_void_p(self._ev_rr.data_ptr()), self._stream())
 
     def eval_resident_step(self):
         """One eager eval batch at the cursor (a step past the end of the split is a no-op).  Returns the batch's
         (pos, neg [max_batch, Kn], rr) buffers; the first B rows are the batch's."""
-        self.finish()
-        self._prefetched = False
+        self._settle()
         self._eval_step()
         Kn = self._ev[3]
         return self.out_pos, self.out_neg[:self.cfg.max_batch * Kn].view(-1, Kn), self.mrr
@@ -1068,8 +1062,7 @@ class TgnEngine:
         if self._ev_graphs is None:
             raise RuntimeError("TgnEngine: no captured eval step (capture_eval after bind_eval_resident; a new binding or "
                                "a grown workspace drops it)")
-        self.finish()
-        self._prefetched = False
+        self._settle()
         g1, k, gk = self._ev_graphs
         done = 0
         while done < n:
@@ -1203,10 +1196,8 @@ class TgnEngine:
         """The next batch's scan (split pipelined steps): rides beside the exchange."""
         if self._split():
             lo, hi, batch = self._res
-            rc = _lib.lib().tgnx_tgn_scan_next(self._cfg_ref, self._buf_ref, lo, hi, batch, self.rank, self.world,
-                                               self.seed, self._stream())
-            if rc:
-                raise RuntimeError(f"tgnx_tgn_scan_next failed: {_lib.lib().tgnx_last_error().decode()}")
+            _lib.call("tgnx_tgn_scan_next", self._cfg_ref, self._buf_ref, lo, hi, batch, self.rank, self.world, self.seed,
+                      self._stream())
 
     def _allreduce(self, between=None):
         """The exchange; `between` (the next batch's scan) runs on the compute stream while it is in flight."""
@@ -1254,11 +1245,9 @@ class TgnEngine:
         state runs this first; replays then take the graph without the apply."""
         if not self._apply_pending:
             return
-        rc = _lib.lib().tgnx_tgn_apply_rows_update(self._cfg_ref, self._buf_ref, ctypes.c_void_p(self.xgather.data_ptr()),
-                                                  ctypes.c_int64(self.xgather.shape[0]), self._stream())
-        self._apply_pending = False
-        if rc:
-            raise RuntimeError(f"tgnx_tgn_apply_rows_update failed: {_lib.lib().tgnx_last_error().decode()}")
+        self._apply_pending = False  # (cleared whether or not the apply succeeds: a failed one is not retried)
+        _lib.call("tgnx_tgn_apply_rows_update", self._cfg_ref, self._buf_ref, ctypes.c_void_p(self.xgather.data_ptr()),
+                  ctypes.c_int64(self.xgather.shape[0]), self._stream())
 
     def capture_resident(self):
         """One resident step as HIP graph(s) (world > 1: the collectives stay eager between them)."""
