@@ -204,6 +204,9 @@ class RefTransformerConv(nn.Module):
         self.lin_value = nn.Linear(in_channels, heads * out_channels)
         self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
         self.lin_skip = nn.Linear(in_channels, heads * out_channels)
+        # tests only: an injected attention-dropout mask [E, H] (0 or 1 / (1 - p)) for the next training forward,
+        # set per step by the caller (conv and conv2 each carry their own); None = F.dropout as in PyG
+        self.keep = None
 
     def forward(self, x, edge_index, edge_attr):
         H, C = self.H, self.C
@@ -212,14 +215,16 @@ class RefTransformerConv(nn.Module):
         k = self.lin_key(x)[j].view(-1, H, C)
         v = self.lin_value(x)[j].view(-1, H, C)
         e = self.lin_edge(edge_attr).view(-1, H, C)
-        out, _ = transformer_attention(q, k, v, e, i, x.size(0), self.dropout if self.training else 0.0)
+        out, _ = transformer_attention(q, k, v, e, i, x.size(0), self.dropout if self.training else 0.0,
+                                       keep=self.keep if self.training else None)
         return out + self.lin_skip(x)
 
 
-def transformer_attention(q, k, v, e, i, N, dropout=0.0):
+def transformer_attention(q, k, v, e, i, N, dropout=0.0, keep=None):
     """[ext] TransformerConv.message + aggregate (concat, beta False): q [E,H,C] (the destination's query per
     edge), k, v, e [E,H,C], destination index i [E].  a = q·(k+e)/sqrt(C); α = softmax per destination (max
-    subtracted, + 1e-16, torch_geometric.utils.softmax); out_i = Σ α (v+e).  Returns (out [N, H*C], α [E, H])."""
+    subtracted, + 1e-16, torch_geometric.utils.softmax); out_i = Σ α (v+e).  Returns (out [N, H*C], α [E, H]).
+    keep [E, H] (values 0 or 1 / (1 - p)): the dropout mask to apply to α in place of F.dropout's own draw."""
     H, C = q.shape[1], q.shape[2]
     k = k + e
     a = (q * k).sum(-1) / math.sqrt(C)                  # [E, H]
@@ -228,7 +233,10 @@ def transformer_attention(q, k, v, e, i, N, dropout=0.0):
     ex = (a - amax[i]).exp()
     den = torch.zeros(N, H, dtype=q.dtype).index_add(0, i, ex) + 1e-16
     alpha = ex / den[i]
-    a = nn.functional.dropout(alpha, p=dropout, training=dropout > 0)
+    if keep is not None:
+        a = alpha * keep.to(alpha.dtype)
+    else:
+        a = nn.functional.dropout(alpha, p=dropout, training=dropout > 0)
     out = (v + e) * a.unsqueeze(-1)
     out = torch.zeros(N, H, C, dtype=q.dtype).index_add(0, i, out).view(N, H * C)
     return out, alpha

@@ -118,6 +118,11 @@ class RefTGNN(nn.Module):
 
     feat_drop / attn_drop default to the reference's hard-coded 0.6 (:664-665); parity
     tests pass 0.0 because dropout RNG streams cannot be shared with the HIP path.
+
+    Tests only: `drop_keeps`, when set, is called once per dependency block as drop_keeps(block index, g, sub_e)
+    and returns (nfeat keep [M, D], efeat keep [|sub_e|, ef_dim + D], attention keep [|sub_e|, H]) or None for any
+    of them: masks with values 0 or 1 / (1 - p) that are multiplied in where the nn.Dropout draw would be (the
+    HIP path's counter-based masks restated, so a dropout-on step can be compared).  Off (None) by default.
     """
 
     def __init__(self, ef_dim, hidden_dim, num_nodes, num_heads=8, feat_drop=0.6, attn_drop=0.6):
@@ -131,17 +136,18 @@ class RefTGNN(nn.Module):
         self.predictor = RefEdgePredictor(D, D)
         self.feat_drop = nn.Dropout(feat_drop)
         self.attn_drop = nn.Dropout(attn_drop)
+        self.drop_keeps = None
 
     # EdgeGATConv.forward (:565-612) + TemporalTransformerConv.forward (:688-697) on the
     # in-subgraph given as (edge ids of g, g) -> embeddings of all g nodes [M, D]
-    def _embed(self, g, sub_e, ef, bt, node_ts, nfeat):
+    def _embed(self, g, sub_e, ef, bt, node_ts, nfeat, nfeat_keep=None, efeat_keep=None, attn_keep=None):
         gat = self.embedding_attn.edge_gatconv
         src, dst = g.src[sub_e], g.dst[sub_e]
         M, H, D = g.num_nodes, self.H, self.D
         tdiff = bt[sub_e] - node_ts[src]                                # :442
         efeat = torch.cat([ef[sub_e], self.temporal_encoder(tdiff)], dim=1)   # :447-448
-        nfeat = self.feat_drop(nfeat)                                   # :579
-        efeat = self.feat_drop(efeat)                                   # :580
+        nfeat = self.feat_drop(nfeat) if nfeat_keep is None else nfeat * nfeat_keep     # :579
+        efeat = self.feat_drop(efeat) if efeat_keep is None else efeat * efeat_keep     # :580
         node_feat = gat.fc_node(nfeat).view(-1, H, D)
         edge_feat = gat.fc_edge(efeat).view(-1, H, D)
         el = (node_feat * gat.attn_l).sum(-1, keepdim=True)
@@ -154,7 +160,8 @@ class RefTGNN(nn.Module):
                                                                       "amax", include_self=True)
         ex = torch.exp(e - emax[dst])
         den = torch.zeros(M, H, 1).index_add(0, dst, ex)
-        a = self.attn_drop(ex / den[dst])
+        a = ex / den[dst]
+        a = self.attn_drop(a) if attn_keep is None else a * attn_keep.view(-1, H, 1)
         ft = torch.zeros(M, H, 1).index_add(0, dst, a * el_prime)       # update_all sum :599
         rst = ft + nfeat.view(M, -1, D)                                 # Identity residual :601-604
         return rst.mean(1)                                              # :693
@@ -175,7 +182,8 @@ class RefTGNN(nn.Module):
             sub_e = g.in_edges_of(assoc[roots])
             node_ts = self.time_assoc[g.nid].view(-1, 1)
             nfeat = self.memory.memory[g.nid]
-            embed = self._embed(g, sub_e, ef, bt, node_ts, nfeat)
+            keeps = self.drop_keeps(idx, g, sub_e) if self.drop_keeps is not None else (None, None, None)
+            embed = self._embed(g, sub_e, ef, bt, node_ts, nfeat, *keeps)
             s_emb.append(embed[assoc[s[idx]]])
             p_emb.append(embed[assoc[p[idx]]])
             n_emb.append(embed[assoc[n[idx].reshape(-1)]])

@@ -1,9 +1,13 @@
 """Side-by-side runner: the HIP TGNN step vs the oracle's faithful per-block restatement.
 
 Both start from the same parameters, the same synthetic stream, the same
-dependency blocks and the same injected negatives; dropout is off (the two
+dependency blocks and the same injected negatives; dropout is off by default (the two
 RNG streams cannot be shared).  Used by tests/test_gpu_tgnn.py and by
 __graft_entry__.smoke().
+
+Pair(feat_drop=, attn_drop=) + train_step(dropout=True): the HIP step runs with dropout on and the
+oracle gets the device's own masks (counter-based hashes, restated in tests/dropout_ref.py) through
+RefTGNN.drop_keeps; edge_ordinals() is the map from an oracle edge to the device's mask key.
 """
 from __future__ import annotations
 
@@ -16,9 +20,33 @@ from oracle.epoch_ref import train_batch as ref_train_batch
 from oracle.sampler_ref import RefLastNeighborLoader
 from oracle.tgnn_ref import RefTGNN
 
+import dropout_ref as dr
+
+CTL_SEED, CTL_NB = 9, 10      # include/tgnx.h TGNX_CTL_SEED, TGNX_CTL_NB
+
+
+def edge_ordinals(g, sub_e):
+    """The ordinal o of each oracle edge of sub_e within its root's segment, as tgnn_meta_collapse's writer
+    numbers a segment (tgnx_tgnn.hip edge_meta_body): the root's valid ring slots in slot order, then the self
+    loop, then the root's in-batch touches of earlier blocks in touch-key order (block, kind 1 = positive
+    destination before kind 2 = source, event).  The oracle's graph lists a node's in-edges in that same order
+    by construction: the sampled ring edges row-major over (node, slot) with valid slots leading each row, then
+    one self loop per node, then per earlier block the s->p edges (root = positive destination) in event order
+    followed by the p->s edges (root = source).  sub_e is ascending and holds every in-edge of its roots, so o
+    is the count of earlier edges of sub_e with the same destination."""
+    dst = g.dst[sub_e].numpy()
+    order = np.argsort(dst, kind="stable")
+    d = dst[order]
+    first = np.r_[0, np.flatnonzero(d[1:] != d[:-1]) + 1]
+    run_start = np.repeat(first, np.diff(np.r_[first, d.size]))
+    o = np.empty(d.size, dtype=np.int64)
+    o[order] = np.arange(d.size) - run_start
+    return o
+
 
 class Pair:
-    def __init__(self, N=400, E=1400, d=172, D=100, K=10, B=200, Kn_eval=20, seed=0, t_max=None, shape=None):
+    def __init__(self, N=400, E=1400, d=172, D=100, K=10, B=200, Kn_eval=20, seed=0, t_max=None, shape=None,
+                 feat_drop=0.0, attn_drop=0.0, hub_every=None):
         from tgnx.engine import TgnnEngine
         from tgnx.model import TGNN, getOptimizer
         from tgnx.sampler import LastNeighborLoader
@@ -32,15 +60,20 @@ class Pair:
         else:       # a named TGB shape (full node count), first E events of its stream
             self.s = make_stream(shape, seed=seed, num_events=E)
             N, d = self.s.num_nodes, self.s.shape.msg_dim
+        if hub_every:     # a hub: the first event's source is the source of every hub_every-th event, so its
+            self.s.src[::hub_every] = self.s.src[0]   # segments gather many in-batch edges of earlier blocks
         self.B, self.K, self.D, self.d, self.N, self.Kn_eval = B, K, D, d, N, Kn_eval
         self.blk = blocks_ref.block_ids(self.s.src, self.s.dst, B)
         self.feats = torch.from_numpy(self.s.msg)
         torch.manual_seed(seed)
+        self.pf, self.pa = float(feat_drop), float(attn_drop)
+        # the oracle draws no mask of its own: with dropout on it is handed the device's (train_step(dropout=True))
         self.ref = RefTGNN(d, D, N, feat_drop=0.0, attn_drop=0.0)
         self.ref_opt = torch.optim.Adam(self.ref.parameters(), lr=1e-4)
         self.ref_loader = RefLastNeighborLoader(N, K)
         sd = {k: v.detach().clone() for k, v in self.ref.named_parameters()}
-        self.model = TGNN(d, D, N, "cuda", ring=K, max_batch=B, max_neg=Kn_eval, feat_drop=0.0, attn_drop=0.0)
+        self.model = TGNN(d, D, N, "cuda", ring=K, max_batch=B, max_neg=Kn_eval, feat_drop=feat_drop,
+                          attn_drop=attn_drop)
         self.model.load_reference_state(sd)
         self.opt = getOptimizer({"gnn": self.model}, 1e-4)
         self.loader = LastNeighborLoader(N, K, device="cuda")
@@ -71,9 +104,76 @@ class Pair:
             self.loader.insert(torch.from_numpy(self.s.src[sl]), torch.from_numpy(self.s.dst[sl]),
                                torch.from_numpy(t32))
 
-    def train_step(self):
+    def device_keeps(self, seed, ring_eid=None):
+        """The RefTGNN.drop_keeps callback of one step: the device's masks under the step seed, per block.
+        Node features and the residual: stream 1, key (blk << 32) ^ node, sub 0, index = feature dim, p = pf.
+        Edge features: stream 2, key (blk << 32) ^ root, sub = the edge's ordinal, index [0, d) the edge-feature
+        columns and [d, d + D) the time-encoding columns.  Attention: stream 3, same key and sub, index = head,
+        p = pa.  Every mask is recorded in self.masks ({stream: [bool keep arrays]}) with the per-edge roots."""
+        d, D, H = self.d, self.D, self.ref.H
+        self.masks = {"nfeat": [], "efeat": [], "attn": [], "attn_root": []}
+
+        def keeps(blk, g, sub_e):
+            nid = g.nid.numpy()
+            root = nid[g.dst[sub_e].numpy()]
+            o = edge_ordinals(g, sub_e)
+            if ring_eid is not None:     # a ring edge's ordinal is its slot in the root's ring row before the batch
+                ring = sub_e.numpy() < ring_eid.shape[0]
+                assert np.array_equal(self.ref_loader.e_id[root[ring], o[ring]], ring_eid[sub_e.numpy()[ring]])
+            hi = np.int64(blk) << 32
+            nb = dr.drop_base(seed, 1, hi ^ nid, 0)
+            eb = dr.drop_base(seed, 2, hi ^ root, o)
+            ab = dr.drop_base(seed, 3, hi ^ root, o)
+            kn = dr.keep_scale(nb[:, None], np.arange(D)[None, :], self.pf)
+            ke = dr.keep_scale(eb[:, None], np.arange(d + D)[None, :], self.pf)
+            ka = dr.keep_scale(ab[:, None], np.arange(H)[None, :], self.pa)
+            touched = np.unique(np.r_[g.src[sub_e].numpy(), g.dst[sub_e].numpy()])   # the rows the block reads
+            self.masks["nfeat"].append(kn[touched] != 0)
+            self.masks["efeat"].append(ke != 0)
+            self.masks["attn"].append(ka != 0)
+            self.masks["attn_root"].append(hi ^ root)
+            return torch.from_numpy(kn), torch.from_numpy(ke), torch.from_numpy(ka)
+        return keeps
+
+    def _train_step_dropout(self, src, dst, t, msg, blk, neg):
+        """The HIP step first (its seed is read back and checked against the restated formula), then the oracle
+        with the device's masks.  Also records `mask_effect`: the largest change of an oracle logit, relative to
+        the largest logit, when the masks are removed."""
+        from oracle.epoch_ref import _assemble
+        pos, negl, _ = self.eng.train_batch(src, dst, t, msg, blk, neg=neg, dropout=True)
+        torch.cuda.synchronize()
+        self.eng.check()
+        pos, negl = pos.cpu().numpy().copy(), negl.cpu().numpy().copy()
+        self.gpu_loss = float(self.model.grad_flat[-1])
+        seed, nb = int(self.eng.ctl[CTL_SEED]), int(self.eng.ctl[CTL_NB])
+        assert seed == dr.step_seed(self.eng.seed, nb), (seed, nb)
+        q = torch.cat([src, dst, neg.reshape(-1)]).unique().numpy()
+        ring_eid = self.ref_loader(q)[2]
+        self.ref.train()
+        with torch.no_grad():       # forward() moves time_assoc: put it back after the two probes
+            ta = self.ref.time_assoc.clone()
+            outs = []
+            for cb in (None, self.device_keeps(seed)):
+                self.ref.drop_keeps = cb
+                g, bf, bt, blocks = _assemble(self.ref_loader, self.feats, src, dst, neg, t, msg, blk)
+                outs.append(torch.cat(self.ref(g, bf, bt, blocks)).view(-1).numpy())
+                self.ref.time_assoc.copy_(ta)
+        self.mask_effect = rel_err(outs[0], outs[1])
+        self.ref.drop_keeps = self.device_keeps(seed, ring_eid)
+        try:
+            ref = ref_train_batch(self.ref, self.ref_opt, self.ref_loader, self.feats, src, dst, neg, t, msg, blk)
+        finally:
+            self.ref.drop_keeps = None
+        return ref, pos, negl
+
+    def train_step(self, dropout=False):
         src, dst, t, msg, blk = self._batch(self.B)
         neg = torch.from_numpy(self.rng.choice(self.s.dst_nodes, size=src.shape[0]))
+        if dropout:
+            (ref_loss, ref_pos, ref_neg), pos, negl = self._train_step_dropout(src, dst, t, msg, blk, neg)
+            order = np.argsort(blk.numpy(), kind="stable")
+            return dict(ref_loss=float(ref_loss), loss=self.gpu_loss, ref_pos=ref_pos.view(-1).numpy(),
+                        pos=pos[order], ref_neg=ref_neg.view(-1).numpy(), neg=negl[order])
         ref_loss, ref_pos, ref_neg = ref_train_batch(self.ref, self.ref_opt, self.ref_loader, self.feats, src, dst,
                                                      neg, t, msg, blk)
         pos, negl, _ = self.eng.train_batch(src, dst, t, msg, blk, neg=neg, dropout=False)
