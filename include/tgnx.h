@@ -659,6 +659,51 @@ int tgnx_link_predictor_topk(int64_t n_src, int64_t n_cand, int64_t d_in, int64_
                              float* out_all /* optional [n_src, n_cand], may be NULL */, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* tgnx_link_predictor_topk with per-source exclusions by key.  All four inputs are optional (NULL): cand_key
+ * [n_cand] (NULL: a candidate's key is its position); src_key [n_src]: candidate c is excluded for source q when
+ * cand_key[c] == src_key[q]; excl_ptr [n_src + 1] and excl_key [nnz]: c is excluded for q when cand_key[c] occurs in
+ * excl_key[excl_ptr[q] : excl_ptr[q + 1]] (each segment ascending, duplicates allowed).  Exclusion is by key, so
+ * every position holding an excluded key is excluded.  An excluded pair is never selected; with fewer than k
+ * candidates left the tail is the padding (idx -1, val -INFINITY, 0 with sigmoid).  out_all gets the UNMASKED logits.
+ * Order, ties and NaN as tgnx_link_predictor_topk; a source without exclusions gets exactly its result, and every
+ * logit has exactly its bits.  excl_ptr values are clamped into [0, nnz] and a decreasing pair reads as an empty
+ * segment; searches stay inside their segment: no content of the arrays causes an access outside their stated sizes
+ * (an unsorted segment gives an unspecified selection for that source, nothing worse).  Same workspace, same
+ * guarantees (no atomics, no allocation, no host synchronisation). */
+size_t tgnx_link_predictor_topk_filtered_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k);
+int tgnx_link_predictor_topk_filtered(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                                      const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                                      const float* b_dst, const float* w_out, const float* b_out, int32_t k,
+                                      int32_t sigmoid, const int64_t* cand_key /* optional [n_cand] */,
+                                      const int64_t* src_key /* optional [n_src] */,
+                                      const int64_t* excl_ptr /* optional [n_src + 1] */,
+                                      const int64_t* excl_key /* [nnz] */, int64_t nnz,
+                                      float* out_val /* [n_src, k] */, int64_t* out_idx /* [n_src, k] */,
+                                      float* out_all /* optional [n_src, n_cand] */, void* ws, size_t ws_bytes,
+                                      void* stream);
+
+/* The same predictor over a candidate list per source: source q is ranked against the positions
+ * list_idx[list_ptr[q] : list_ptr[q + 1]] into z_cand (list_ptr [n_src + 1], list_idx [nnz]; max_len: the host's
+ * upper bound on a list's length).  An entry < 0 is skipped silently (how a caller masks an entry); an entry >=
+ * n_cand, or at offset >= max_len in its list, is skipped and counted: *n_invalid (optional, device) is incremented.
+ * Duplicate entries are separate entries.  out_val [n_src, k]; out_idx [n_src, k] candidate positions; out_slot
+ * [n_src, k] the entry's offset inside the source's list; out_logits (optional, [nnz]) every entry's logit, NaN at a
+ * skipped entry.  Order: larger logit first, equal logits by lower slot; padding idx / slot -1, val -INFINITY (0 with
+ * sigmoid).  Hs and Hd come from the two GEMMs of tgnx_link_predictor_topk and the per-entry logit is its fma chain:
+ * for the same inputs the logit of (q, c) has the bits of its out_all[q][c].  list_ptr values are clamped into
+ * [0, nnz], a decreasing pair reads as an empty list.  No atomics except the invalid counter, no allocation, no host
+ * synchronisation.  ws: tgnx_link_predictor_topk_lists_ws_bytes bytes (monotone in n_cand and max_len). */
+size_t tgnx_link_predictor_topk_lists_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k,
+                                               int64_t max_len);
+int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                                   const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                                   const float* b_dst, const float* w_out, const float* b_out, int32_t k,
+                                   int32_t sigmoid, const int64_t* list_ptr /* [n_src + 1] */,
+                                   const int64_t* list_idx /* [nnz] */, int64_t nnz, int64_t max_len,
+                                   float* out_val /* [n_src, k] */, int64_t* out_idx /* [n_src, k] */,
+                                   int64_t* out_slot /* [n_src, k] */, float* out_logits /* optional [nnz] */,
+                                   int64_t* n_invalid /* optional, device */, void* ws, size_t ws_bytes, void* stream);
+
 /* TransformerConv's attention (modules/emb_module.py:21-29; PyG TransformerConv, concat, no beta): for
  * destination i with incoming edges p in [indptr[i], indptr[i+1]) (rows of the per-edge k, v, e [E, H*C];
  * q [n_dst, H*C]), per head h: a_p = q_i·(k_p + e_p) / sqrt(C), α = softmax over i's edges (max subtracted,

@@ -25,6 +25,12 @@
 // Chunks rather than one workgroup per source tile walking every candidate: 200 sources are 13 tiles, 13 workgroups
 // on 256 CUs; chunked, the wiki shape (200 x 9,227) is 13 x 37 workgroups.  Partials cost n_src · chunks · k · 8 B.
 // No atomics, no allocation, no host synchronisation: graph-capturable, run-to-run identical.
+//
+// Two more entry points share Hs / Hd, the fma chain, the order and topk_merge:
+//   tgnx_link_predictor_topk_filtered   per-source exclusions by key: topk_pairs<true> writes NaN over an excluded
+//                                       pair's LDS entry after out_all got the logit;
+//   tgnx_link_predictor_topk_lists      a candidate list per source: topk_list_pairs, one workgroup per (source,
+//                                       chunk of the list), positions = slots in the list; topk_list_idx.
 #include <limits.h>
 #include <math.h>
 
@@ -41,6 +47,8 @@ constexpr int TK_TQ = 16;        // sources per workgroup (four per wave in the 
 constexpr int TK_CHUNK_MIN = 256, TK_CHUNK_MAX = 512;  // candidates per workgroup (LDS: 16 x chunk logits, <= 32 KB)
 constexpr int64_t TK_DMAX = 256;
 constexpr int TK_G = 4;          // 16-B vectors of a candidate's Hd row per load group (two groups in registers)
+constexpr int TK_EXCAP = 1024;  // exclusion keys of a source tile staged in LDS (8 KB; above: searched in global memory)
+constexpr int TK_LCHUNK = 256;  // list entries per workgroup of the per-source-list kernel (one per thread)
 constexpr int TK_MTILE = 896;    // partial entries per merge pass (+ the running list: 1024 entries, 8 KB per wave)
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -86,11 +94,43 @@ __device__ __forceinline__ void wave_best(float& bv, int& bj) {
   bv = m;
 }
 
+// Per-source exclusions by key (tgnx_link_predictor_topk_filtered): candidate c is out for source q when its key
+// (cand_key[c], or c itself) equals src_key[q] or occurs in excl_key[excl_ptr[q] : excl_ptr[q + 1]] (ascending).
+struct TopkFilter {
+  const int64_t *cand_key, *src_key, *excl_ptr, *excl_key;
+  int64_t nnz;
+};
+// LDS beside the logits (filtered kernel): the tile's exclusion segments when they fit, their bounds, the source keys
+struct TopkFilterLds {
+  int64_t key[TK_EXCAP];
+  int64_t lo[TK_TQ], hi[TK_TQ], skey[TK_TQ];
+  int off[TK_TQ];
+  int has_skey[TK_TQ];
+  int staged;
+};
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// key in a[lo, hi)?  A lower bound that never leaves [lo, hi), whatever the segment holds
+template <typename Int>
+__device__ __forceinline__ bool seg_has(const int64_t* a, Int lo, Int hi, int64_t key) {
+  Int n = hi - lo;
+  while (n > 0) {
+    const Int half = n >> 1;
+    if (a[lo + half] < key) {
+      lo += half + 1;
+      n -= half + 1;
+    } else {
+      n = half;
+    }
+  }
+  return lo < hi && a[lo] == key;
+}
+
+template <bool FILT>
 __global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_cand, int D, int ldh, int chunk, int nc,
                                                        const float* __restrict__ hs, const float* __restrict__ hd,
                                                        const float* __restrict__ w_out, const float* __restrict__ b_out,
                                                        int k, float* __restrict__ pval, int* __restrict__ pidx,
-                                                       float* __restrict__ out_all) {
+                                                       float* __restrict__ out_all, TopkFilter f) {
   extern __shared__ __attribute__((aligned(16))) float tk_smem[];
   float* hsT = tk_smem;                     // [ldh][16] the tile's Hs rows, k-major; rows past n_src and columns past D zero
   float* wl = hsT + (size_t)ldh * TK_TQ;    // [ldh] w_out, zero past D
@@ -100,6 +140,39 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_
   const int64_t cbase = (int64_t)(blockIdx.x % nc) * chunk;
   const int nq = (int)min((int64_t)TK_TQ, n_src - q0);
   const int nvalid = (int)min((int64_t)chunk, n_cand - cbase);
+  // (ldh and chunk are multiples of 4: the struct starts 16-B aligned)
+  TopkFilterLds* X = reinterpret_cast<TopkFilterLds*>(L + (size_t)TK_TQ * chunk);
+  if constexpr (FILT) {
+    // the tile's segments, their pointers clamped into [0, nnz] and a decreasing pair read as empty; staged in LDS
+    // when the tile's keys fit (ring rows: 16 x <= 32), searched in global memory otherwise
+    if (tid < TK_TQ) {
+      int64_t lo = 0, hi = 0;
+      if (f.excl_ptr && tid < nq) {
+        lo = clamp64(f.excl_ptr[q0 + tid], 0, f.nnz);
+        hi = max(lo, clamp64(f.excl_ptr[q0 + tid + 1], 0, f.nnz));
+      }
+      X->lo[tid] = lo;
+      X->hi[tid] = hi;
+      X->has_skey[tid] = f.src_key && tid < nq;
+      X->skey[tid] = (f.src_key && tid < nq) ? f.src_key[q0 + tid] : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int64_t tot = 0;
+      for (int i = 0; i < TK_TQ; ++i) {
+        X->off[i] = (int)min(tot, (int64_t)TK_EXCAP);
+        tot += X->hi[i] - X->lo[i];
+      }
+      X->staged = tot <= TK_EXCAP;
+    }
+    __syncthreads();
+    if (X->staged)
+      for (int i = 0; i < TK_TQ; ++i) {
+        const int64_t lo = X->lo[i];
+        const int len = (int)(X->hi[i] - lo), off = X->off[i];
+        for (int x = tid; x < len; x += TK_BLOCK) X->key[off + x] = f.excl_key[lo + x];
+      }
+  }
   for (int x = tid; x < ldh * TK_TQ; x += TK_BLOCK) {
     const int kk = x / TK_TQ, q = x % TK_TQ;
     hsT[x] = (q < nq && kk < D) ? hs[(q0 + q) * ldh + kk] : 0.f;
@@ -149,10 +222,26 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_
         }
       }
     }
+    // an excluded pair's entry in LDS becomes NaN, which the select never picks; out_all keeps the logit
+    unsigned excl = 0;
+    if constexpr (FILT) {
+      const int64_t cpos = cbase + min(cl, nvalid - 1);
+      const int64_t ck = f.cand_key ? f.cand_key[cpos] : cpos;
+      const bool staged = X->staged;
+      for (int i = 0; i < nq; ++i) {
+        bool out = X->has_skey[i] && X->skey[i] == ck;
+        const int64_t lo = X->lo[i], hi = X->hi[i];
+        if (!out && hi > lo)
+          out = staged ? seg_has<int>(X->key, X->off[i], X->off[i] + (int)(hi - lo), ck)
+                       : seg_has<int64_t>(f.excl_key, lo, hi, ck);
+        excl |= (unsigned)out << i;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < TK_TQ; ++i) {
       const float lg = acc[i] + bo;
-      L[i * chunk + cl] = lg;  // (entries past nvalid are never scanned)
+      // (entries past nvalid are never scanned)
+      L[i * chunk + cl] = (FILT && ((excl >> i) & 1u)) ? __int_as_float(0x7fc00000) : lg;
       if (out_all && valid && i < nq) out_all[(q0 + i) * n_cand + cbase + cl] = lg;
     }
   }
@@ -294,6 +383,202 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_merge(int64_t n_src, int nc, in
   }
 }
 
+// Per-source candidate lists (tgnx_link_predictor_topk_lists): one workgroup per (source, chunk of TK_LCHUNK list
+// entries).  Hs[q] and w_out sit in LDS; a thread owns one entry and streams its gathered Hd row 16 B at a time through
+// the same fma chain as topk_pairs (k ascending over the padded row, the pad columns zero), so the logit of (q, c) has
+// the bits of the dense operator's.  Wave 0 then picks the chunk's k best by the same pick-after-previous selection,
+// positions being slots in the source's list.  Skipped entries (negative, >= n_cand, slot >= max_len) hold NaN.  The
+// list's bounds are clamped into [0, nnz]; slots past the grid's reach (>= nc * TK_LCHUNK) are swept by the last chunk.
+__global__ void __launch_bounds__(TK_LCHUNK) topk_list_pairs(int64_t n_cand, int D, int ldh, int nc, int64_t nnz,
+                                                             int64_t max_len, const int64_t* __restrict__ list_ptr,
+                                                             const int64_t* __restrict__ list_idx,
+                                                             const float* __restrict__ hs, const float* __restrict__ hd,
+                                                             const float* __restrict__ w_out,
+                                                             const float* __restrict__ b_out, int k,
+                                                             float* __restrict__ pval, int* __restrict__ pidx,
+                                                             float* __restrict__ out_logits,
+                                                             unsigned long long* __restrict__ n_invalid) {
+  extern __shared__ __attribute__((aligned(16))) float tl_smem[];
+  float* hq = tl_smem;       // [ldh] Hs[q], zero past D
+  float* wl = hq + ldh;      // [ldh] w_out, zero past D
+  float* L = wl + ldh;       // [TK_LCHUNK] the chunk's logits
+  __shared__ int bad_sh[TK_LCHUNK / WAVE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t q = blockIdx.x / nc;
+  const int cj = (int)(blockIdx.x % nc);
+  const int64_t lo = clamp64(list_ptr[q], 0, nnz), hi = max(lo, clamp64(list_ptr[q + 1], 0, nnz));
+  const int64_t len = hi - lo;
+  for (int x = tid; x < ldh; x += TK_LCHUNK) {
+    hq[x] = x < D ? hs[q * ldh + x] : 0.f;
+    wl[x] = x < D ? w_out[x] : 0.f;
+  }
+  __syncthreads();
+  const float qnan = __int_as_float(0x7fc00000);
+  const int64_t s = (int64_t)cj * TK_LCHUNK + tid;
+  int bad = 0;
+  float lg = qnan;
+  if (s < len) {
+    const int64_t c = list_idx[lo + s];
+    const bool within = s < max_len;
+    bad = !within || c >= n_cand;
+    if (within && c >= 0 && c < n_cand) {
+      const float4* row = reinterpret_cast<const float4*>(hd + c * ldh);
+      const int nv = ldh >> 2;
+      float acc = 0.f;
+      float4 nxt[TK_G];
+#pragma unroll
+      for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
+      for (int v0 = 0; v0 < nv; v0 += TK_G) {
+        float4 cur[TK_G];
+#pragma unroll
+        for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
+#pragma unroll
+        for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
+#pragma unroll
+        for (int u = 0; u < TK_G; ++u) {
+          if (v0 + u >= nv) break;
+          const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int kk = (v0 + u) * 4 + e;
+            const float hv = kk < D ? he[e] : 0.f;
+            acc = fmaf(wl[kk], fmaxf(hq[kk] + hv, 0.f), acc);
+          }
+        }
+      }
+      lg = acc + b_out[0];
+    }
+    if (out_logits) out_logits[lo + s] = lg;
+  }
+  L[tid] = lg;
+  if (cj == nc - 1)
+    for (int64_t t = (int64_t)nc * TK_LCHUNK + tid; t < len; t += TK_LCHUNK) {
+      if (out_logits) out_logits[lo + t] = qnan;
+      bad += 1;
+    }
+  if (n_invalid) {  // (block-uniform) the one atomic: an integer count
+    int b = bad;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b += __shfl_xor(b, o, WAVE);
+    if (lane == 0) bad_sh[tid >> 6] = b;
+  }
+  __syncthreads();
+  if (tid >= WAVE) return;
+  if (n_invalid && tid == 0) {
+    int b = 0;
+    for (int w = 0; w < TK_LCHUNK / WAVE; ++w) b += bad_sh[w];
+    if (b) atomicAdd(n_invalid, (unsigned long long)b);
+  }
+  const int nvalid = (int)max((int64_t)0, min((int64_t)TK_LCHUNK, len - (int64_t)cj * TK_LCHUNK));
+  float pv = INFINITY;
+  int pj = -1;
+  for (int r = 0; r < k; ++r) {
+    float bv = -INFINITY;
+    int bj = INT_MAX;
+    for (int j = lane; j < nvalid; j += WAVE) {
+      const float v = L[j];
+      if (after(v, j, pv, pj) && (v > bv || bj == INT_MAX)) {
+        bv = v;
+        bj = j;
+      }
+    }
+    wave_best(bv, bj);
+    if (lane == 0) {
+      pval[(q * nc + cj) * k + r] = bj == INT_MAX ? -INFINITY : L[bj];
+      pidx[(q * nc + cj) * k + r] = bj == INT_MAX ? -1 : cj * TK_LCHUNK + bj;
+    }
+    pv = bv;
+    pj = bj;
+  }
+}
+
+// out_idx[q][r] = the candidate position at the selected slot of q's list (-1 at the padding)
+__global__ void __launch_bounds__(TK_BLOCK) topk_list_idx(int64_t n_src, int k, int64_t nnz,
+                                                          const int64_t* __restrict__ list_ptr,
+                                                          const int64_t* __restrict__ list_idx,
+                                                          const int64_t* __restrict__ out_slot,
+                                                          int64_t* __restrict__ out_idx) {
+  const int64_t x = blockIdx.x * (int64_t)TK_BLOCK + threadIdx.x;
+  if (x >= n_src * k) return;
+  const int64_t q = x / k, slot = out_slot[x];
+  const int64_t at = clamp64(list_ptr[q], 0, nnz) + slot;
+  out_idx[x] = (slot >= 0 && at < nnz) ? list_idx[at] : -1;
+}
+
+struct ListWs {
+  float *hs, *hd, *pval;
+  int* pidx;
+  char* gemm;
+  size_t used;
+  int64_t nc;
+};
+ListWs list_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D, int32_t k, int64_t max_len) {
+  const int64_t ldh = ld_of(D);
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = 0;
+  ListWs w;
+  w.nc = std::max<int64_t>(1, ceil_div(max_len, TK_LCHUNK));
+  w.hs = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_src * ldh * 4);
+  w.hd = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_cand * ldh * 4);
+  w.pval = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_src * w.nc * k * 4);
+  w.pidx = reinterpret_cast<int*>(p + off);
+  off += align256((size_t)n_src * w.nc * k * 4);
+  w.gemm = p + off;
+  w.used = off;
+  return w;
+}
+
+// the dense operator with or without exclusions (f == nullptr: the launches tgnx_link_predictor_topk always made)
+int topk_dense(const char* name, int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+               const float* z_cand, const float* w_src, const float* b_src, const float* w_dst, const float* b_dst,
+               const float* w_out, const float* b_out, int32_t k, int32_t sigmoid, const TopkFilter* f, float* out_val,
+               int64_t* out_idx, float* out_all, void* ws, size_t ws_bytes, void* stream) {
+  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "%s: k must be in [1, %d], got %d", name, TGNX_TOPK_MAX, k);
+  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
+                     n_cand < (int64_t(1) << 31) - TK_CHUNK_MAX && n_src < (int64_t(1) << 31),
+                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
+  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && (n_src == 0 || (z_src && out_val && out_idx)) &&
+                     (n_cand == 0 || z_cand),
+                 "%s: null pointer", name);
+  if (f)
+    TGNX_CHECK_ARG(f->nnz >= 0 && (!f->excl_ptr || f->nnz == 0 || f->excl_key),
+                   "%s: excl_ptr needs excl_key and nnz >= 0", name);
+  TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_topk_ws_bytes(n_src, n_cand, d_in, D, k), "%s: workspace too small",
+                 name);
+  if (n_src == 0) return TGNX_OK;
+  hipStream_t s = as_stream(stream);
+  const TopkWs w = topk_ws(ws, n_src, n_cand, D, k);
+  const int64_t ldh = ld_of(D);
+  const int chunk = chunk_of(n_src, n_cand);
+  const int64_t nc = ceil_div(n_cand, chunk), blocks = ceil_div(n_src, TK_TQ) * nc;
+  TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "%s: n_src x n_cand beyond one launch's grid", name);
+  if (n_cand > 0) {
+    const size_t gbytes = ws_bytes - w.used;
+    int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
+    if (rc != TGNX_OK) return rc;
+    rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
+    if (rc != TGNX_OK) return rc;
+    if (f)
+      hipLaunchKernelGGL(topk_pairs<true>, dim3((unsigned)blocks), dim3(TK_BLOCK),
+                         pairs_smem(ldh, chunk) + sizeof(TopkFilterLds), s, n_src, n_cand, (int)D, (int)ldh, chunk,
+                         (int)nc, (const float*)w.hs, (const float*)w.hd, w_out, b_out, (int)k, w.pval, w.pidx, out_all,
+                         *f);
+    else
+      hipLaunchKernelGGL(topk_pairs<false>, dim3((unsigned)blocks), dim3(TK_BLOCK), pairs_smem(ldh, chunk), s, n_src,
+                         n_cand, (int)D, (int)ldh, chunk, (int)nc, (const float*)w.hs, (const float*)w.hd, w_out, b_out,
+                         (int)k, w.pval, w.pidx, out_all, TopkFilter{});
+    TGNX_LAUNCH_CHECK("topk_pairs");
+  }
+  // (n_cand = 0: no chunk, every slot is padding)
+  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src, (int)nc,
+                     (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_idx);
+  TGNX_LAUNCH_CHECK("topk_merge");
+  return TGNX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -311,37 +596,77 @@ int tgnx_link_predictor_topk(int64_t n_src, int64_t n_cand, int64_t d_in, int64_
                              const float* b_dst, const float* w_out, const float* b_out, int32_t k, int32_t sigmoid,
                              float* out_val, int64_t* out_idx, float* out_all, void* ws, size_t ws_bytes,
                              void* stream) {
-  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "tgnx_link_predictor_topk: k must be in [1, %d], got %d", TGNX_TOPK_MAX, k);
+  return topk_dense("tgnx_link_predictor_topk", n_src, n_cand, d_in, D, z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out,
+                    b_out, k, sigmoid, nullptr, out_val, out_idx, out_all, ws, ws_bytes, stream);
+}
+
+size_t tgnx_link_predictor_topk_filtered_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k) {
+  return tgnx_link_predictor_topk_ws_bytes(n_src, n_cand, d_in, D, k);
+}
+
+int tgnx_link_predictor_topk_filtered(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                                      const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                                      const float* b_dst, const float* w_out, const float* b_out, int32_t k,
+                                      int32_t sigmoid, const int64_t* cand_key, const int64_t* src_key,
+                                      const int64_t* excl_ptr, const int64_t* excl_key, int64_t nnz, float* out_val,
+                                      int64_t* out_idx, float* out_all, void* ws, size_t ws_bytes, void* stream) {
+  const TopkFilter f{cand_key, src_key, excl_ptr, excl_key, nnz};
+  return topk_dense("tgnx_link_predictor_topk_filtered", n_src, n_cand, d_in, D, z_src, z_cand, w_src, b_src, w_dst,
+                    b_dst, w_out, b_out, k, sigmoid, &f, out_val, out_idx, out_all, ws, ws_bytes, stream);
+}
+
+size_t tgnx_link_predictor_topk_lists_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k,
+                                               int64_t max_len) {
+  if (n_src < 0 || n_cand < 0 || d_in <= 0 || D <= 0 || D > TK_DMAX || k < 1 || k > TGNX_TOPK_MAX || max_len < 0)
+    return 256;
+  const ListWs w = list_ws(nullptr, n_src, n_cand, D, k, max_len);
+  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
+                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
+  return w.used + align256(g) + 256;
+}
+
+int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                                   const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                                   const float* b_dst, const float* w_out, const float* b_out, int32_t k,
+                                   int32_t sigmoid, const int64_t* list_ptr, const int64_t* list_idx, int64_t nnz,
+                                   int64_t max_len, float* out_val, int64_t* out_idx, int64_t* out_slot,
+                                   float* out_logits, int64_t* n_invalid, void* ws, size_t ws_bytes, void* stream) {
+  const char* name = "tgnx_link_predictor_topk_lists";
+  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "%s: k must be in [1, %d], got %d", name, TGNX_TOPK_MAX, k);
   TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
-                     n_cand < (int64_t(1) << 31) - TK_CHUNK_MAX && n_src < (int64_t(1) << 31),
-                 "tgnx_link_predictor_topk: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", (int)TK_DMAX);
-  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && (n_src == 0 || (z_src && out_val && out_idx)) &&
-                     (n_cand == 0 || z_cand),
-                 "tgnx_link_predictor_topk: null pointer");
-  TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_topk_ws_bytes(n_src, n_cand, d_in, D, k),
-                 "tgnx_link_predictor_topk: workspace too small");
+                     n_cand < (int64_t(1) << 31) && n_src < (int64_t(1) << 31),
+                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
+  TGNX_CHECK_ARG(nnz >= 0 && max_len >= 0 && max_len < (int64_t(1) << 31) - TK_LCHUNK,
+                 "%s: nnz and max_len must be >= 0 (max_len < 2^31 - %d)", name, TK_LCHUNK);
+  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && list_ptr && (nnz == 0 || list_idx) &&
+                     (n_src == 0 || (z_src && out_val && out_idx && out_slot)) && (n_cand == 0 || z_cand),
+                 "%s: null pointer", name);
+  TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_topk_lists_ws_bytes(n_src, n_cand, d_in, D, k, max_len),
+                 "%s: workspace too small", name);
   if (n_src == 0) return TGNX_OK;
   hipStream_t s = as_stream(stream);
-  const TopkWs w = topk_ws(ws, n_src, n_cand, D, k);
-  const int64_t ldh = ld_of(D);
-  const int chunk = chunk_of(n_src, n_cand);
-  const int64_t nc = ceil_div(n_cand, chunk), blocks = ceil_div(n_src, TK_TQ) * nc;
-  TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "tgnx_link_predictor_topk: n_src x n_cand beyond one launch's grid");
-  if (n_cand > 0) {
+  const ListWs w = list_ws(ws, n_src, n_cand, D, k, max_len);
+  const int64_t ldh = ld_of(D), blocks = n_src * w.nc;
+  TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "%s: n_src x max_len beyond one launch's grid", name);
+  if (n_cand > 0) {  // the dense operator's two GEMMs, the same shapes
     const size_t gbytes = ws_bytes - w.used;
     int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
     if (rc != TGNX_OK) return rc;
     rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
     if (rc != TGNX_OK) return rc;
-    hipLaunchKernelGGL(topk_pairs, dim3((unsigned)blocks), dim3(TK_BLOCK), pairs_smem(ldh, chunk), s, n_src, n_cand,
-                       (int)D, (int)ldh, chunk, (int)nc, (const float*)w.hs, (const float*)w.hd, w_out, b_out, (int)k,
-                       w.pval, w.pidx, out_all);
-    TGNX_LAUNCH_CHECK("topk_pairs");
   }
-  // (n_cand = 0: no chunk, every slot is padding)
-  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src, (int)nc,
-                     (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_idx);
+  // (n_cand = 0: Hs is not computed and not used, every entry is skipped)
+  hipLaunchKernelGGL(topk_list_pairs, dim3((unsigned)blocks), dim3(TK_LCHUNK), (size_t)(2 * ldh + TK_LCHUNK) * 4, s,
+                     n_cand, (int)D, (int)ldh, (int)w.nc, nnz, max_len, list_ptr, list_idx, (const float*)w.hs,
+                     (const float*)w.hd, w_out, b_out, (int)k, w.pval, w.pidx, out_logits,
+                     reinterpret_cast<unsigned long long*>(n_invalid));
+  TGNX_LAUNCH_CHECK("topk_list_pairs");
+  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src,
+                     (int)w.nc, (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_slot);
   TGNX_LAUNCH_CHECK("topk_merge");
+  hipLaunchKernelGGL(topk_list_idx, dim3((unsigned)ceil_div(n_src * k, TK_BLOCK)), dim3(TK_BLOCK), 0, s, n_src, (int)k,
+                     nnz, list_ptr, list_idx, (const int64_t*)out_slot, out_idx);
+  TGNX_LAUNCH_CHECK("topk_list_idx");
   return TGNX_OK;
 }
 

@@ -365,6 +365,102 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk(
   return {val, idx, all};
 }
 
+// the argument checks predictor_topk makes, shared by its filtered and per-source-list forms; returns (d_in, D)
+std::pair<int64_t, int64_t> topk_args(const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src,
+                                      const at::Tensor& w_dst, const at::Tensor& w_out, const at::Tensor& b_out,
+                                      int64_t k) {
+  dev_tensor(z_src, at::kFloat, "z_src");
+  dev_tensor(z_cand, at::kFloat, "z_cand");
+  dev_tensor(w_src, at::kFloat, "w_src");
+  dev_tensor(w_dst, at::kFloat, "w_dst");
+  dev_tensor(w_out, at::kFloat, "w_out");
+  dev_tensor(b_out, at::kFloat, "b_out");
+  TORCH_CHECK(z_src.dim() == 2 && z_cand.dim() == 2 && z_src.size(1) == z_cand.size(1), "z_src [B, d] and z_cand [C, d]");
+  const int64_t d_in = z_src.size(1), D = w_src.size(0);
+  TORCH_CHECK(w_src.dim() == 2 && w_src.size(1) == d_in && w_dst.dim() == 2 && w_dst.size(0) == D &&
+                  w_dst.size(1) == d_in,
+              "w_src / w_dst must be [D, d]");
+  TORCH_CHECK(w_out.numel() == D && b_out.numel() == 1, "w_out must have D entries and b_out one");
+  TORCH_CHECK(k >= 1 && k <= TGNX_TOPK_MAX, "k must be in [1, ", TGNX_TOPK_MAX, "], got ", k);
+  same_device(z_src, {&z_cand, &w_src, &w_dst, &w_out, &b_out});
+  return {d_in, D};
+}
+
+const int64_t* opt_long(const c10::optional<at::Tensor>& x, const at::Tensor& ref, int64_t numel, const char* name) {
+  if (!x.has_value()) return nullptr;
+  dev_tensor(*x, at::kLong, name);
+  TORCH_CHECK(numel < 0 || x->numel() == numel, name, " must have ", numel, " entries");
+  same_device(ref, {&*x});
+  return x->data_ptr<int64_t>();
+}
+
+// predictor_topk with per-source exclusions by key (tgnx_link_predictor_topk_filtered); the logits are unmasked
+std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk_filtered(
+    const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src,
+    const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out,
+    int64_t k, bool sigmoid, bool return_scores, const c10::optional<at::Tensor>& cand_key,
+    const c10::optional<at::Tensor>& src_key, const c10::optional<at::Tensor>& excl_ptr,
+    const c10::optional<at::Tensor>& excl_key) {
+  const auto [d_in, D] = topk_args(z_src, z_cand, w_src, w_dst, w_out, b_out, k);
+  const int64_t B = z_src.size(0), C = z_cand.size(0);
+  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
+  const int64_t* ck = opt_long(cand_key, z_src, C, "cand_key");
+  const int64_t* sk = opt_long(src_key, z_src, B, "src_key");
+  const int64_t* ep = opt_long(excl_ptr, z_src, B + 1, "excl_ptr");
+  const int64_t* ek = opt_long(excl_key, z_src, -1, "excl_key");
+  TORCH_CHECK(!ep || excl_key.has_value(), "excl_ptr needs excl_key");
+  const int64_t nnz = excl_key.has_value() ? excl_key->numel() : 0;
+  const c10::OptionalDeviceGuard guard(z_src.device());
+  at::Tensor val = at::empty({B, k}, z_src.options());
+  at::Tensor idx = at::empty({B, k}, z_src.options().dtype(at::kLong));
+  at::Tensor all = return_scores ? at::empty({B, C}, z_src.options()) : at::empty({0}, z_src.options());
+  const size_t nb = tgnx_link_predictor_topk_filtered_ws_bytes(B, C, d_in, D, (int32_t)k);
+  at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
+  check_rc(tgnx_link_predictor_topk_filtered(
+               B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(), w_src.data_ptr<float>(), bs,
+               w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(), b_out.data_ptr<float>(), (int32_t)k,
+               sigmoid ? 1 : 0, ck, sk, ep, ek, nnz, val.data_ptr<float>(), idx.data_ptr<int64_t>(),
+               return_scores ? all.data_ptr<float>() : nullptr, ws.data_ptr(), nb, cur_stream()),
+           "tgnx_link_predictor_topk_filtered");
+  return {val, idx, all};
+}
+
+// LinkPredictor + top-k over a candidate list per source (tgnx_link_predictor_topk_lists):
+// (val [B, k], idx [B, k], slot [B, k], logits [nnz] or empty, n_invalid [1])
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_topk_lists(
+    const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src,
+    const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out,
+    int64_t k, bool sigmoid, bool return_scores, const at::Tensor& list_ptr, const at::Tensor& list_idx,
+    int64_t max_len) {
+  const auto [d_in, D] = topk_args(z_src, z_cand, w_src, w_dst, w_out, b_out, k);
+  const int64_t B = z_src.size(0), C = z_cand.size(0), nnz = list_idx.numel();
+  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
+  dev_tensor(list_ptr, at::kLong, "list_ptr");
+  dev_tensor(list_idx, at::kLong, "list_idx");
+  TORCH_CHECK(list_ptr.numel() == B + 1, "list_ptr must have n_src + 1 entries");
+  TORCH_CHECK(max_len >= 0, "max_len must be >= 0");
+  same_device(z_src, {&list_ptr, &list_idx});
+  const c10::OptionalDeviceGuard guard(z_src.device());
+  at::Tensor val = at::empty({B, k}, z_src.options());
+  at::Tensor idx = at::empty({B, k}, z_src.options().dtype(at::kLong));
+  at::Tensor slot = at::empty({B, k}, z_src.options().dtype(at::kLong));
+  at::Tensor logits = return_scores ? at::empty({nnz}, z_src.options()) : at::empty({0}, z_src.options());
+  at::Tensor bad = at::zeros({1}, z_src.options().dtype(at::kLong));
+  const size_t nb = tgnx_link_predictor_topk_lists_ws_bytes(B, C, d_in, D, (int32_t)k, max_len);
+  at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
+  check_rc(tgnx_link_predictor_topk_lists(
+               B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(), w_src.data_ptr<float>(), bs,
+               w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(), b_out.data_ptr<float>(), (int32_t)k,
+               sigmoid ? 1 : 0, list_ptr.data_ptr<int64_t>(), list_idx.data_ptr<int64_t>(), nnz, max_len,
+               val.data_ptr<float>(), idx.data_ptr<int64_t>(), slot.data_ptr<int64_t>(),
+               return_scores ? logits.data_ptr<float>() : nullptr, bad.data_ptr<int64_t>(), ws.data_ptr(), nb,
+               cur_stream()),
+           "tgnx_link_predictor_topk_lists");
+  return {val, idx, slot, logits, bad};
+}
+
 void attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const c10::optional<at::Tensor>& e,
                const at::Tensor& indptr, int64_t heads) {
   dev_tensor(q, at::kFloat, "q");
@@ -822,6 +918,14 @@ TORCH_LIBRARY(tgnx, m) {
   m.def("predictor_topk(Tensor z_src, Tensor z_cand, Tensor w_src, Tensor? b_src, Tensor w_dst, Tensor? b_dst, "
         "Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores) -> (Tensor, Tensor, Tensor)",
         &predictor_topk);
+  m.def("predictor_topk_filtered(Tensor z_src, Tensor z_cand, Tensor w_src, Tensor? b_src, Tensor w_dst, "
+        "Tensor? b_dst, Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores, Tensor? cand_key, "
+        "Tensor? src_key, Tensor? excl_ptr, Tensor? excl_key) -> (Tensor, Tensor, Tensor)",
+        &predictor_topk_filtered);
+  m.def("predictor_topk_lists(Tensor z_src, Tensor z_cand, Tensor w_src, Tensor? b_src, Tensor w_dst, Tensor? b_dst, "
+        "Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores, Tensor list_ptr, Tensor list_idx, "
+        "int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
+        &predictor_topk_lists);
   m.def("predictor_bwd(Tensor dout, Tensor z_src, Tensor z_dst, Tensor w_src, Tensor? b_src, Tensor w_dst, "
         "Tensor? b_dst, Tensor w_out, Tensor b_out, bool sigmoid, int[] need) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",

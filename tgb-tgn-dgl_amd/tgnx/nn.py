@@ -203,6 +203,16 @@ class LinkPredictor(nn.Module):
                              self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, k, sigmoid=True,
                              return_scores=return_scores)
 
+    def topk_filtered(self, z_src, z_cand, k, return_scores=False, *, cand_key=None, src_key=None, exclude=None,
+                      lists=None, validate=True, max_len=None):
+        """topk with ops.link_topk's per-source keywords forwarded: exclusions by key (cand_key, src_key, exclude =
+        (ptr, keys)) return (val, idx[, logits]); a candidate list per source (lists = (ptr, positions)) returns
+        (val, idx, slot[, ragged logits]).  With none of them given it is topk."""
+        return ops.link_topk(z_src, z_cand, self.lin_src.weight, self.lin_src.bias, self.lin_dst.weight,
+                             self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, k, sigmoid=True,
+                             return_scores=return_scores, cand_key=cand_key, src_key=src_key, exclude=exclude,
+                             lists=lists, validate=validate, max_len=max_len)
+
 
 class TGNMemory(nn.Module):
     """modules/memory_module.py:25-215 over a device message store (csrc/tgnx_memstore.hip).

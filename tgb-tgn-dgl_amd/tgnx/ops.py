@@ -9,7 +9,8 @@ tcsr_sample (TGL t-CSR, utils.py:73), gemm_f32 (MFMA fp32 GEMM), and the TGN mod
 (csrc/tgnx_ops.hip): msg_agg_last / msg_agg_mean (LastAggregator / MeanAggregator, modules/msg_agg.py:15-26),
 gru_update (TGNMemory's GRUCell / RNNCell, memory_module.py:70-78), predictor (LinkPredictor decoder.py:12-27;
 EdgePredictor model_utils.py:165-195), predictor_topk (LinkPredictor over all pairs with the top-k selection fused
-in, csrc/tgnx_topk.hip; `link_topk` below) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
+in, csrc/tgnx_topk.hip; `link_topk` below; predictor_topk_filtered / predictor_topk_lists: the same with per-source
+exclusions by key / a candidate list per source) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
 emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function), time_encode (TimeEncoder)
 and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
 gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd, msg_agg_mean_bwd) sit
@@ -29,6 +30,7 @@ import torch
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "predictor_topk", "edge_attn_fwd", "edge_attn_bwd",
+       "predictor_topk_filtered", "predictor_topk_lists",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
@@ -158,17 +160,80 @@ def link_predictor(z_src, z_dst, w_src, b_src, w_dst, b_dst, w_out, b_out, sigmo
                                 bool(sigmoid))
 
 
+def _ragged(pair, n_src, dev, what, validate, need_sorted):
+    """(ptr, values) as contiguous int64 device tensors and the longest segment (None without `validate`).
+    validate: ONE host read checks ptr[0] == 0, ptr non-decreasing, ptr[-1] == len(values) and (need_sorted) every
+    segment ascending; ValueError otherwise."""
+    ptr, vals = pair
+    ptr = torch.as_tensor(ptr).to(dev, torch.long).contiguous().view(-1)
+    vals = torch.as_tensor(vals).to(dev, torch.long).contiguous().view(-1)
+    if ptr.numel() != n_src + 1:
+        raise ValueError(f"link_topk: {what} ptr must have n_src + 1 = {n_src + 1} entries, got {ptr.numel()}")
+    if not validate:
+        return ptr, vals, None
+    nnz = vals.numel()
+    lens = ptr[1:] - ptr[:-1]
+    ok_ptr = (ptr[0] == 0) & (ptr[-1] == nnz) & (lens >= 0).all()
+    ok_sorted = torch.ones((), dtype=torch.bool, device=dev)
+    if need_sorted and nnz > 1:
+        start = torch.zeros(nnz + 1, dtype=torch.bool, device=dev)
+        start[ptr.clamp(0, nnz)] = True            # a descent across a segment boundary is none
+        ok_sorted = ~((vals[1:] < vals[:-1]) & ~start[1:nnz]).any()
+    longest = lens.max() if n_src else torch.zeros((), dtype=torch.long, device=dev)
+    ok_ptr, ok_sorted, longest = torch.stack([ok_ptr.long(), ok_sorted.long(), longest]).tolist()
+    if not ok_ptr:
+        raise ValueError(f"link_topk: {what} ptr must start at 0, not decrease and end at len(values) = {nnz}")
+    if not ok_sorted:
+        raise ValueError(f"link_topk: every {what} segment must be ascending")
+    return ptr, vals, int(longest)
+
+
 @torch.no_grad()
-def link_topk(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, k, sigmoid=True, return_scores=False):
+def link_topk(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, k, sigmoid=True, return_scores=False,
+              cand_key=None, src_key=None, exclude=None, lists=None, validate=True, max_len=None):
     """The k best candidates of every source under LinkPredictor (decoder.py:12-27), scored over all n_src x n_cand
     pairs and selected in the same kernel (tgnx_link_predictor_topk): no [n_src * n_cand, d] operand, no score
     matrix handed to torch.topk.  Returns (val [n_src, k], idx [n_src, k]) and, with return_scores, the logits
     [n_src, n_cand] the selection compared.  idx holds positions into z_cand, ordered by larger logit, equal logits
     by lower position; val the logits, or their sigmoid (sigmoid=True); slots past n_cand hold idx -1 and val -inf
-    (0 with sigmoid).  The selection is always on the logit.  Inference only: no autograd."""
+    (0 with sigmoid).  The selection is always on the logit.  Inference only: no autograd.
+
+    Per-source exclusions (tgnx_link_predictor_topk_filtered; any of cand_key, src_key, exclude given): a candidate's
+    key is cand_key[c] (int64 [n_cand]; default its position); it is left out for source q when the key equals
+    src_key[q] (int64 [n_src]) or occurs in q's segment of exclude = (ptr [n_src + 1], keys), each segment ascending.
+    Excluded pairs are never selected (padding when fewer than k remain); the returned logits are unmasked.
+
+    A candidate list per source (tgnx_link_predictor_topk_lists; lists = (ptr [n_src + 1], positions into z_cand)):
+    returns (val, idx, slot[, logits [nnz]]) with slot the entry's offset in its list and equal logits ordered by
+    lower slot; an entry < 0 is skipped, one >= n_cand too (NaN in logits).  max_len: an upper bound on a list's
+    length (default: the longest list when validated, else len(positions)).  Not combined with the exclusions:
+    mask an entry by writing -1.
+
+    validate: one host read per ragged argument checks ptr[0] == 0, ptr non-decreasing, ptr[-1] == len(values) and,
+    for exclude, ascending segments (ValueError).  Without it the kernels still keep every access inside the arrays."""
     c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
-    val, idx, logits = load().predictor_topk(c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out),
-                                             c(b_out), int(k), bool(sigmoid), bool(return_scores))
+    if cand_key is None and src_key is None and exclude is None and lists is None:
+        val, idx, logits = load().predictor_topk(c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out),
+                                                 c(b_out), int(k), bool(sigmoid), bool(return_scores))
+        return (val, idx, logits) if return_scores else (val, idx)
+    dev, n_src = z_src.device, z_src.size(0)
+    key = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.long).contiguous().view(-1)  # noqa: E731
+    if lists is not None:
+        if cand_key is not None or src_key is not None or exclude is not None:
+            raise ValueError("link_topk: lists is not combined with cand_key / src_key / exclude (mask entries with -1)")
+        ptr, pos, longest = _ragged(lists, n_src, dev, "lists", validate, need_sorted=False)
+        if max_len is None:
+            max_len = pos.numel() if longest is None else longest
+        val, idx, slot, logits, _ = load().predictor_topk_lists(
+            c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out), c(b_out), int(k), bool(sigmoid),
+            bool(return_scores), ptr, pos, int(max_len))
+        return (val, idx, slot, logits) if return_scores else (val, idx, slot)
+    ptr = keys = None
+    if exclude is not None:
+        ptr, keys, _ = _ragged(exclude, n_src, dev, "exclude", validate, need_sorted=True)
+    val, idx, logits = load().predictor_topk_filtered(
+        c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out), c(b_out), int(k), bool(sigmoid),
+        bool(return_scores), key(cand_key), key(src_key), ptr, keys)
     return (val, idx, logits) if return_scores else (val, idx)
 
 

@@ -984,6 +984,121 @@ class TgnEngine:
         ids = torch.where(idx >= 0, cand[idx.clamp(min=0)], idx) if cand.numel() else idx
         return (out[0], ids) + tuple(out[2:])
 
+    def _ragged_ids(self, x, n_src, what):
+        """(ptr [n_src + 1], node ids, longest segment) on the device from a (ptr, ids) tuple of tensors / arrays or a
+        sequence of n_src sequences; the ids checked against [0, N) and the pointers for shape (host reads)."""
+        from . import ops
+        if not (isinstance(x, tuple) and len(x) == 2 and all(isinstance(a, (torch.Tensor, np.ndarray)) for a in x)):
+            rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in x]
+            if len(rows) != n_src:
+                raise ValueError(f"{what}: {len(rows)} lists for {n_src} sources")
+            ptr = np.zeros(n_src + 1, dtype=np.int64)
+            np.cumsum([r.size for r in rows], out=ptr[1:])
+            x = (ptr, np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64))
+        ptr, ids, longest = ops._ragged(x, n_src, self.dev, what, True, need_sorted=False)
+        N = self.cfg.num_nodes
+        if ids.numel() and bool(((ids < 0) | (ids >= N)).any()):
+            raise ValueError(f"{what}: node ids must be in [0, {N})")
+        return ptr, ids, longest
+
+    def _segments(self, ptr, nnz):
+        """The source row of every entry of a ragged array."""
+        q = torch.arange(ptr.numel() - 1, device=self.dev)
+        return torch.repeat_interleave(q, ptr[1:] - ptr[:-1], output_size=nnz)
+
+    def _exclusions(self, src, exclude_seen, exclude):
+        """(ptr [Q + 1], keys) of the per-source exclusions, each segment ascending: the valid entries of the source's
+        neighbour-ring row (e_id >= 0; reset_state leaves stale ids in `neighbors`) and the caller's lists.  Invalid
+        ring slots become the key N, which no node carries.  Device ops only; None when nothing is excluded."""
+        N, Q = self.cfg.num_nodes, src.numel()
+        seg, key = [], []
+        if exclude_seen:
+            ld = self.loader
+            rows = torch.where(ld.e_id[src] >= 0, ld.neighbors[src], torch.full_like(ld.neighbors[src], N))
+            key.append(rows.reshape(-1))
+            seg.append(torch.arange(Q, device=self.dev).repeat_interleave(rows.shape[1]))
+        if exclude is not None:
+            ptr, ids, _ = self._ragged_ids(exclude, Q, "recommend: exclude")
+            key.append(ids)
+            seg.append(self._segments(ptr, ids.numel()))
+        if not key:
+            return None
+        comp = torch.sort(torch.cat(seg) * (N + 1) + torch.cat(key)).values        # by source, then by key
+        ptr = torch.searchsorted(comp, torch.arange(Q + 1, device=self.dev) * (N + 1))
+        return ptr, comp % (N + 1), comp
+
+    @torch.no_grad()
+    def recommend_filtered(self, src, k: int, candidates=None, return_scores: bool = False, *,
+                           exclude_seen: bool = False, exclude_self: bool = False, exclude=None, per_source=None):
+        """recommend() with per-source exclusions and per-source candidate lists; read-only in the same way.
+        exclude_seen: leave out the nodes in the source's neighbour-ring row (its most recent interaction partners).
+        exclude_self: leave out the source itself.  exclude: more node ids per source, a (ptr, node_ids) tuple of
+        tensors / arrays or a sequence of sequences, one per source.  Exclusion is by node id, so every position of a
+        duplicated candidate goes.  Returns recommend()'s tuple; the logits are unmasked.
+        per_source (not with `candidates`): every source's own candidate list, in the same two forms.  The engine
+        embeds src and the distinct listed nodes once and ranks each source over its list only
+        (ops.link_topk(lists=...)): equal logits by the entry's place in the list; excluded entries are masked in a
+        private copy.  Returns (val [Q, k], node_ids [Q, k][, logits [nnz]]), the logits aligned with the caller's
+        entries and NaN at an excluded one."""
+        from . import ops
+        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        Q, N = src.numel(), self.cfg.num_nodes
+        if Q and bool(((src < 0) | (src >= N)).any()):
+            raise ValueError(f"recommend: node ids must be in [0, {N})")
+        lp = self.model.link_pred
+        w = (lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight,
+             lp.lin_final.bias)
+        ex = self._exclusions(src, exclude_seen, exclude)
+        if per_source is not None:
+            if candidates is not None:
+                raise ValueError("recommend: per_source and candidates are mutually exclusive")
+            ptr, ids, longest = self._ragged_ids(per_source, Q, "recommend: per_source")
+            uniq, pos = torch.unique(ids, return_inverse=True)
+            z = self.embed(torch.cat([src, uniq]))
+            seg = self._segments(ptr, ids.numel())
+            pos = pos.clone()
+            if exclude_self:
+                pos[ids == src[seg]] = -1
+            if ex is not None and ex[2].numel():
+                comp = seg * (N + 1) + ids
+                at = torch.searchsorted(ex[2], comp).clamp(max=ex[2].numel() - 1)
+                pos[ex[2][at] == comp] = -1
+            out = ops.link_topk(z[:Q], z[Q:], *w, k, sigmoid=True, return_scores=return_scores, lists=(ptr, pos),
+                                validate=False, max_len=longest)
+            idx = out[1]
+            node = torch.where(idx >= 0, uniq[idx.clamp(min=0)], idx) if uniq.numel() else idx
+            return (out[0], node) + tuple(out[3:])
+        if ex is None and not exclude_self:
+            return self.recommend(src, k, candidates=candidates, return_scores=return_scores)
+        if candidates is None:
+            candidates = self.dst_nodes if self.dst_nodes is not None else torch.arange(N, device=self.dev)
+        cand = torch.as_tensor(candidates).to(self.dev, torch.long).contiguous().view(-1)
+        z = self.embed(torch.cat([src, cand]))
+        out = ops.link_topk(z[:Q], z[Q:], *w, k, sigmoid=True, return_scores=return_scores, cand_key=cand,
+                            src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2],
+                            validate=False)
+        idx = out[1]
+        ids = torch.where(idx >= 0, cand[idx.clamp(min=0)], idx) if cand.numel() else idx
+        return (out[0], ids) + tuple(out[2:])
+
+    @torch.no_grad()
+    def score(self, src, dst) -> torch.Tensor:
+        """The model's link probability [n] for the explicit pairs (src[i], dst[i]) at the current stream state:
+        embed() of both lists, then the LinkPredictor operator.  Read-only as embed() is."""
+        from . import ops
+        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        dst = torch.as_tensor(dst).to(self.dev, torch.long).contiguous().view(-1)
+        if src.numel() != dst.numel():
+            raise ValueError(f"score: {src.numel()} sources for {dst.numel()} destinations")
+        n = src.numel()
+        z = self.embed(torch.cat([src, dst]))
+        if n == 0:
+            return z.new_empty(0)
+        lp = self.model.link_pred
+        return ops.link_predictor(z[:n].contiguous(), z[n:].contiguous(), lp.lin_src.weight, lp.lin_src.bias,
+                                  lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight, lp.lin_final.bias,
+                                  sigmoid=True).view(-1)
+
     # ------------------------------------------------------------------ resident eval pass
     def bind_eval_resident(self, split_lo: int, split_hi: int, batch: int, negs):
         """A validation / test pass over events [split_lo, split_hi) in batches of `batch`, resident on the device:

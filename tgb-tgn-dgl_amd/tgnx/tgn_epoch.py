@@ -18,6 +18,8 @@ updates the stores, the memory and the ring in eval order.
 
   recommend(model, neighbor_loader, src, k, candidates=None) -> (val [Q, k], node_ids [Q, k]): the k destinations
       the trained model ranks highest for each source at the current stream state (TgnEngine.recommend; read-only)
+  recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclude_seen, exclude_self, exclude,
+      per_source): the same with per-source exclusions or per-source candidate lists (TgnEngine.recommend_filtered)
   observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
       table and taken into memory, stores and ring as test() batches would leave them, without negatives or scores
       (TgnEngine.observe_events)
@@ -195,6 +197,23 @@ def recommend(model, neighbor_loader, src, k, candidates=None):
         eng.flush()
         eng._mode_train = False
     return eng.recommend(src, k, candidates=candidates)
+
+
+@torch.no_grad()
+def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclude_seen=False, exclude_self=False,
+                       exclude=None, per_source=None):
+    """recommend() with per-source exclusions (exclude_seen: the source's recent interaction partners; exclude_self;
+    exclude: more node ids per source) or a candidate list per source (per_source), TgnEngine.recommend_filtered's
+    keywords passed through.  Read-only; switches the memory to eval first as recommend() does."""
+    eng = getattr(_owner(model), "_tgnx_engine", None)
+    if eng is None or eng.loader is not neighbor_loader:
+        raise RuntimeError("tgnx recommend_filtered: no engine bound to this model / neighbor_loader yet (run train() "
+                           "or test() first: they bind the event table)")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    return eng.recommend_filtered(src, k, candidates=candidates, exclude_seen=exclude_seen, exclude_self=exclude_self,
+                                  exclude=exclude, per_source=per_source)
 
 
 @torch.no_grad()
