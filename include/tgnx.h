@@ -704,6 +704,34 @@ int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, 
                                    int64_t* out_slot /* [n_src, k] */, float* out_logits /* optional [nnz] */,
                                    int64_t* n_invalid /* optional, device */, void* ws, size_t ws_bytes, void* stream);
 
+/* Where each source's true destination stands among the candidates (csrc/tgnx_topk.hip): the counts
+ * a filtered rank needs, without the [n_src, n_cand] logits and without a selection.  z_src, z_cand and the weights
+ * as tgnx_link_predictor_topk; only the first n_count <= n_cand rows of z_cand compete (rows past them exist so that
+ * a target need not be a competitor); target [n_src]: the position in z_cand of source q's true destination.
+ * cand_key, src_key, excl_ptr, excl_key, nnz: optional, with the meaning and the clamping of
+ * tgnx_link_predictor_topk_filtered.  With key(c) = cand_key ? cand_key[c] : c, p = target[q] and logit(q, c) the
+ * bits of tgnx_link_predictor_topk's out_all[q][c] on the same operands (the same two GEMMs, the same fma chain),
+ * the compared set S_q is every c in [0, n_count) with c != p, key(c) != key(p) (the target's node never competes
+ * with itself, duplicates included), key(c) != src_key[q], key(c) not in q's exclusion segment, and logit(q, c) not
+ * NaN.  The target itself is never removed by the exclusions.  Outputs, each [n_src]: out_tlogit = tl = logit(q, p);
+ * out_gt = #{c in S_q: logit > tl}; out_eq = #{c in S_q: logit == tl} (float ==: -0 equals +0); out_n = |S_q|.  The
+ * rank under TGB's convention is 1 + gt + eq / 2.  A skipped row (p < 0, p >= n_cand, or tl NaN): gt = eq = 0,
+ * tlogit = NaN, n as defined (p out of range: the key(p) rule is vacuous).  n_src = 0 does nothing.  excl_ptr values
+ * are clamped into [0, nnz], a decreasing pair reads as an empty segment, a target is read only inside [0, n_cand):
+ * no content of the arrays causes an access outside their stated sizes.  Integer atomics only (exact, run-to-run
+ * identical), no allocation, no host synchronisation: graph-capturable.  D <= 256.
+ * ws: tgnx_link_predictor_rank_ws_bytes bytes (Hs, Hd, the GEMM's; monotone in n_cand). */
+size_t tgnx_link_predictor_rank_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D);
+int tgnx_link_predictor_rank(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                             const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                             const float* b_dst, const float* w_out, const float* b_out, int64_t n_count,
+                             const int64_t* target /* [n_src] */, const int64_t* cand_key /* optional [n_cand] */,
+                             const int64_t* src_key /* optional [n_src] */,
+                             const int64_t* excl_ptr /* optional [n_src + 1] */,
+                             const int64_t* excl_key /* [nnz] */, int64_t nnz, int64_t* out_gt /* [n_src] */,
+                             int64_t* out_eq /* [n_src] */, int64_t* out_n /* [n_src] */,
+                             float* out_tlogit /* [n_src] */, void* ws, size_t ws_bytes, void* stream);
+
 /* TransformerConv's attention (modules/emb_module.py:21-29; PyG TransformerConv, concat, no beta): for
  * destination i with incoming edges p in [indptr[i], indptr[i+1]) (rows of the per-edge k, v, e [E, H*C];
  * q [n_dst, H*C]), per head h: a_p = q_i·(k_p + e_p) / sqrt(C), α = softmax over i's edges (max subtracted,

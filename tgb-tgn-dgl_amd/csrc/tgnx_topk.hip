@@ -31,6 +31,22 @@
 //                                       pair's LDS entry after out_all got the logit;
 //   tgnx_link_predictor_topk_lists      a candidate list per source: topk_list_pairs, one workgroup per (source,
 //                                       chunk of the list), positions = slots in the list; topk_list_idx.
+//
+// tgnx_link_predictor_rank wants less than a selection: where each source's true destination stands
+// among the candidates, i.e. per source three counts (logits above the target's, equal to it, compared at all).  Same
+// Hs / Hd GEMMs, same chain, same exclusion staging; no LDS logit matrix, no select rounds, no merge:
+//   rank_target  a wave per source: tl[q] = logit(q, target[q]) by the chain over the padded row (as
+//                topk_list_pairs does for a list entry; NaN at a target outside z_cand), and the three counters zeroed;
+//   rank_pairs   one workgroup per (tile of 16 sources, chunk of 256 candidates), a thread per candidate: its 16
+//                logits against the tile's 16 tl in LDS, the key rules, then per source a ballot and a population
+//                count per counter (scalar instructions: exact, and cheaper than three DPP sums), the four waves'
+//                counts through LDS, one 64-bit integer atomicAdd per (source, counter) and chunk.
+// The chunk is 256 = one candidate per thread.  Without the [16][chunk] logits nothing rewards a larger one but the
+// Hs staging (6.4 KB of LDS writes against ~19 k VALU cycles per wave at D = 100), and at 200 x 9,227 it gives
+// 13 x 37 = 481 workgroups of four waves on 256 CUs, at most two waves per SIMD, all resident at once; 512 would
+// leave a fifth of the CUs with one workgroup against others' two of twice the length, and 128 changes nothing (the
+// same waves).  Integer atomics commute: run-to-run identical.  No float atomics, no allocation, no host
+// synchronisation.
 #include <limits.h>
 #include <math.h>
 
@@ -505,6 +521,219 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_list_idx(int64_t n_src, int k, 
   out_idx[x] = (slot >= 0 && at < nnz) ? list_idx[at] : -1;
 }
 
+// ---------------------------------------------------------------- rank of a given target (tgnx_link_predictor_rank)
+// tl[q] = logit(q, target[q]): topk_list_pairs' per-entry chain (k ascending over the padded row, the pad columns
+// zero), so the bits of the dense operator's out_all[q][target[q]]; NaN at a target outside [0, n_cand).  A wave per
+// source: the lanes load the two rows once, coalesced, and leave w_k and relu(Hs[q][k] + Hd[p][k]) in LDS; lane 0
+// then runs the chain's fmas in order.  (A thread per source walking both rows took 9.7 us at 200 x 9,227 x 100:
+// seven dependent rounds of loads.)  The three counters start at zero here, before rank_pairs adds to them.
+__global__ void __launch_bounds__(TK_BLOCK) rank_target(int64_t n_src, int64_t n_cand, int D, int ldh,
+                                                        const int64_t* __restrict__ target,
+                                                        const float* __restrict__ hs, const float* __restrict__ hd,
+                                                        const float* __restrict__ w_out,
+                                                        const float* __restrict__ b_out, float* __restrict__ tlogit,
+                                                        unsigned long long* __restrict__ gt,
+                                                        unsigned long long* __restrict__ eq,
+                                                        unsigned long long* __restrict__ n) {
+  constexpr int WPB = TK_BLOCK / WAVE;
+  __shared__ float sw[WPB][TK_DMAX], st[WPB][TK_DMAX];  // (ldh <= TK_DMAX)
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t q = blockIdx.x * (int64_t)WPB + wv;
+  const bool live = q < n_src;  // (wave-uniform; a dead wave keeps the block's barrier)
+  const int64_t p = live ? target[q] : -1;
+  const bool inside = p >= 0 && p < n_cand;
+  if (inside)
+    for (int kk = lane; kk < ldh; kk += WAVE) {
+      const bool in = kk < D;  // (the rows' pad columns are not written by the GEMM)
+      sw[wv][kk] = in ? w_out[kk] : 0.f;
+      st[wv][kk] = fmaxf((in ? hs[q * ldh + kk] : 0.f) + (in ? hd[p * ldh + kk] : 0.f), 0.f);
+    }
+  __syncthreads();
+  if (!live || lane != 0) return;
+  float lg = __int_as_float(0x7fc00000);
+  if (inside) {
+    float acc = 0.f;
+    for (int kk = 0; kk < ldh; ++kk) acc = fmaf(sw[wv][kk], st[wv][kk], acc);
+    lg = acc + b_out[0];
+  }
+  tlogit[q] = lg;
+  gt[q] = 0;
+  eq[q] = 0;
+  n[q] = 0;
+}
+
+// LDS of rank_pairs behind hsT and wl: the tile's targets and the waves' counts
+struct RankLds {
+  int64_t tkey[TK_TQ];  // key(target), where the target lies inside z_cand
+  float tl[TK_TQ];
+  int thas[TK_TQ];
+  int cnt[TK_BLOCK / WAVE][3 * TK_TQ];
+};
+
+// One workgroup per (tile of 16 sources, chunk of TK_BLOCK competing candidates), a thread per candidate; the pair
+// loop is topk_pairs'.  Candidate c counts for source i when its logit is not NaN, its key is not the target's (which
+// covers c == target), not the source's and not in the source's segment.  With tl NaN (a skipped row) neither
+// comparison holds: gt = eq = 0 and n is still the size of the compared set.
+template <bool FILT>
+__global__ void __launch_bounds__(TK_BLOCK) rank_pairs(int64_t n_src, int64_t n_cand, int64_t n_count, int D, int ldh,
+                                                       int nc, const float* __restrict__ hs,
+                                                       const float* __restrict__ hd, const float* __restrict__ w_out,
+                                                       const float* __restrict__ b_out,
+                                                       const int64_t* __restrict__ target,
+                                                       const float* __restrict__ tlogit, TopkFilter f,
+                                                       unsigned long long* __restrict__ gt,
+                                                       unsigned long long* __restrict__ eq,
+                                                       unsigned long long* __restrict__ n) {
+  extern __shared__ __attribute__((aligned(16))) float rk_smem[];
+  float* hsT = rk_smem;                    // [ldh][16] as in topk_pairs
+  float* wl = hsT + (size_t)ldh * TK_TQ;   // [ldh]
+  RankLds* R = reinterpret_cast<RankLds*>(wl + ldh);  // (17 ldh floats: 16-B aligned)
+  TopkFilterLds* X = reinterpret_cast<TopkFilterLds*>(R + 1);
+  const int tid = threadIdx.x;
+  const int64_t tile = blockIdx.x / nc, q0 = tile * TK_TQ;
+  const int64_t cbase = (int64_t)(blockIdx.x % nc) * TK_BLOCK;
+  const int nq = (int)min((int64_t)TK_TQ, n_src - q0);
+  const int nvalid = (int)min((int64_t)TK_BLOCK, n_count - cbase);  // (>= 1: the grid covers [0, n_count))
+  if (tid < TK_TQ) {
+    const int64_t p = tid < nq ? target[q0 + tid] : -1;
+    const bool in = p >= 0 && p < n_cand;
+    R->thas[tid] = in;
+    R->tkey[tid] = in ? (f.cand_key ? f.cand_key[p] : p) : 0;
+    R->tl[tid] = tid < nq ? tlogit[q0 + tid] : __int_as_float(0x7fc00000);
+  }
+  if constexpr (FILT) {
+    // topk_pairs<true>'s staging: pointers clamped into [0, nnz], a decreasing pair empty, LDS when the keys fit
+    if (tid < TK_TQ) {
+      int64_t lo = 0, hi = 0;
+      if (f.excl_ptr && tid < nq) {
+        lo = clamp64(f.excl_ptr[q0 + tid], 0, f.nnz);
+        hi = max(lo, clamp64(f.excl_ptr[q0 + tid + 1], 0, f.nnz));
+      }
+      X->lo[tid] = lo;
+      X->hi[tid] = hi;
+      X->has_skey[tid] = f.src_key && tid < nq;
+      X->skey[tid] = (f.src_key && tid < nq) ? f.src_key[q0 + tid] : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int64_t tot = 0;
+      for (int i = 0; i < TK_TQ; ++i) {
+        X->off[i] = (int)min(tot, (int64_t)TK_EXCAP);
+        tot += X->hi[i] - X->lo[i];
+      }
+      X->staged = tot <= TK_EXCAP;
+    }
+    __syncthreads();
+    if (X->staged)
+      for (int i = 0; i < TK_TQ; ++i) {
+        const int64_t lo = X->lo[i];
+        const int len = (int)(X->hi[i] - lo), off = X->off[i];
+        for (int x = tid; x < len; x += TK_BLOCK) X->key[off + x] = f.excl_key[lo + x];
+      }
+  }
+  for (int x = tid; x < ldh * TK_TQ; x += TK_BLOCK) {
+    const int kk = x / TK_TQ, q = x % TK_TQ;
+    hsT[x] = (q < nq && kk < D) ? hs[(q0 + q) * ldh + kk] : 0.f;
+  }
+  for (int x = tid; x < ldh; x += TK_BLOCK) wl[x] = x < D ? w_out[x] : 0.f;
+  __syncthreads();
+  const float bo = b_out[0];
+  const bool valid = tid < nvalid;
+  // a thread past the chunk's end reads the last valid row (in bounds, counted nowhere)
+  const int64_t cpos = cbase + min(tid, nvalid - 1);
+  const float4* row = reinterpret_cast<const float4*>(hd + cpos * ldh);
+  float acc[TK_TQ];
+#pragma unroll
+  for (int i = 0; i < TK_TQ; ++i) acc[i] = 0.f;
+  const int nv = ldh >> 2;
+  float4 nxt[TK_G];
+#pragma unroll
+  for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
+  for (int v0 = 0; v0 < nv; v0 += TK_G) {
+    float4 cur[TK_G];
+#pragma unroll
+    for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
+#pragma unroll
+    for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
+#pragma unroll
+    for (int u = 0; u < TK_G; ++u) {
+      if (v0 + u >= nv) break;  // (uniform)
+      const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int kk = (v0 + u) * 4 + e;
+        const float hv = kk < D ? he[e] : 0.f;
+        const float wk = wl[kk];
+        const float4* hq = reinterpret_cast<const float4*>(hsT + kk * TK_TQ);
+#pragma unroll
+        for (int g = 0; g < TK_TQ / 4; ++g) {
+          const float4 s = hq[g];
+          acc[4 * g + 0] = fmaf(wk, fmaxf(s.x + hv, 0.f), acc[4 * g + 0]);
+          acc[4 * g + 1] = fmaf(wk, fmaxf(s.y + hv, 0.f), acc[4 * g + 1]);
+          acc[4 * g + 2] = fmaf(wk, fmaxf(s.z + hv, 0.f), acc[4 * g + 2]);
+          acc[4 * g + 3] = fmaf(wk, fmaxf(s.w + hv, 0.f), acc[4 * g + 3]);
+        }
+      }
+    }
+  }
+  const int64_t ck = f.cand_key ? f.cand_key[cpos] : cpos;
+  unsigned excl = 0;
+  if constexpr (FILT) {
+    const bool staged = X->staged;
+    for (int i = 0; i < nq; ++i) {
+      bool out = X->has_skey[i] && X->skey[i] == ck;
+      const int64_t lo = X->lo[i], hi = X->hi[i];
+      if (!out && hi > lo)
+        out = staged ? seg_has<int>(X->key, X->off[i], X->off[i] + (int)(hi - lo), ck)
+                     : seg_has<int64_t>(f.excl_key, lo, hi, ck);
+      excl |= (unsigned)out << i;
+    }
+  }
+  const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+  for (int i = 0; i < TK_TQ; ++i) {
+    const float lg = acc[i] + bo, tl = R->tl[i];
+    const bool in = valid && lg == lg && !(R->thas[i] && R->tkey[i] == ck) && !((excl >> i) & 1u);
+    const int cn = __popcll(__ballot(in)), cg = __popcll(__ballot(in && lg > tl)), ce = __popcll(__ballot(in && lg == tl));
+    if (lane == 0) {
+      R->cnt[wv][3 * i + 0] = cg;
+      R->cnt[wv][3 * i + 1] = ce;
+      R->cnt[wv][3 * i + 2] = cn;
+    }
+  }
+  __syncthreads();
+  if (tid < 3 * TK_TQ) {
+    const int i = tid / 3, which = tid % 3;
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < TK_BLOCK / WAVE; ++w) sum += R->cnt[w][tid];
+    if (i < nq && sum > 0) atomicAdd((which == 0 ? gt : (which == 1 ? eq : n)) + q0 + i, (unsigned long long)sum);
+  }
+}
+
+size_t rank_smem(int64_t ldh, bool filt) {
+  return (size_t)(ldh * TK_TQ + ldh) * sizeof(float) + sizeof(RankLds) + (filt ? sizeof(TopkFilterLds) : 0);
+}
+
+struct RankWs {
+  float *hs, *hd;
+  char* gemm;
+  size_t used;
+};
+RankWs rank_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D) {
+  const int64_t ldh = ld_of(D);
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = 0;
+  RankWs w;
+  w.hs = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_src * ldh * 4);
+  w.hd = reinterpret_cast<float*>(p + off);
+  off += align256((size_t)n_cand * ldh * 4);
+  w.gemm = p + off;
+  w.used = off;
+  return w;
+}
+
 struct ListWs {
   float *hs, *hd, *pval;
   int* pidx;
@@ -667,6 +896,69 @@ int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, 
   hipLaunchKernelGGL(topk_list_idx, dim3((unsigned)ceil_div(n_src * k, TK_BLOCK)), dim3(TK_BLOCK), 0, s, n_src, (int)k,
                      nnz, list_ptr, list_idx, (const int64_t*)out_slot, out_idx);
   TGNX_LAUNCH_CHECK("topk_list_idx");
+  return TGNX_OK;
+}
+
+size_t tgnx_link_predictor_rank_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D) {
+  if (n_src < 0 || n_cand < 0 || d_in <= 0 || D <= 0 || D > TK_DMAX) return 256;
+  const RankWs w = rank_ws(nullptr, n_src, n_cand, D);
+  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
+                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
+  return w.used + align256(g) + 256;
+}
+
+int tgnx_link_predictor_rank(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
+                             const float* z_cand, const float* w_src, const float* b_src, const float* w_dst,
+                             const float* b_dst, const float* w_out, const float* b_out, int64_t n_count,
+                             const int64_t* target, const int64_t* cand_key, const int64_t* src_key,
+                             const int64_t* excl_ptr, const int64_t* excl_key, int64_t nnz, int64_t* out_gt,
+                             int64_t* out_eq, int64_t* out_n, float* out_tlogit, void* ws, size_t ws_bytes,
+                             void* stream) {
+  const char* name = "tgnx_link_predictor_rank";
+  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
+                     n_cand < (int64_t(1) << 31) - TK_BLOCK && n_src < (int64_t(1) << 31),
+                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
+  TGNX_CHECK_ARG(n_count >= 0 && n_count <= n_cand, "%s: n_count must be in [0, n_cand], got %lld", name,
+                 (long long)n_count);
+  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws &&
+                     (n_src == 0 || (z_src && target && out_gt && out_eq && out_n && out_tlogit)) &&
+                     (n_cand == 0 || z_cand),
+                 "%s: null pointer", name);
+  TGNX_CHECK_ARG(nnz >= 0 && (!excl_ptr || nnz == 0 || excl_key), "%s: excl_ptr needs excl_key and nnz >= 0", name);
+  TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_rank_ws_bytes(n_src, n_cand, d_in, D), "%s: workspace too small",
+                 name);
+  if (n_src == 0) return TGNX_OK;
+  hipStream_t s = as_stream(stream);
+  const RankWs w = rank_ws(ws, n_src, n_cand, D);
+  const int64_t ldh = ld_of(D);
+  const int64_t nc = ceil_div(n_count, TK_BLOCK), blocks = ceil_div(n_src, TK_TQ) * nc;
+  TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "%s: n_src x n_count beyond one launch's grid", name);
+  if (n_cand > 0) {  // the dense operator's two GEMMs, the same shapes
+    const size_t gbytes = ws_bytes - w.used;
+    int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
+    if (rc != TGNX_OK) return rc;
+    rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
+    if (rc != TGNX_OK) return rc;
+  }
+  // (n_cand = 0: Hs is not computed and not used, every row is skipped)
+  unsigned long long* gt = reinterpret_cast<unsigned long long*>(out_gt);
+  unsigned long long* eq = reinterpret_cast<unsigned long long*>(out_eq);
+  unsigned long long* nn = reinterpret_cast<unsigned long long*>(out_n);
+  hipLaunchKernelGGL(rank_target, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src, n_cand,
+                     (int)D, (int)ldh, target, (const float*)w.hs, (const float*)w.hd, w_out, b_out, out_tlogit, gt, eq,
+                     nn);
+  TGNX_LAUNCH_CHECK("rank_target");
+  if (n_count == 0) return TGNX_OK;
+  const TopkFilter f{cand_key, src_key, excl_ptr, excl_key, nnz};
+  if (src_key || excl_ptr)
+    hipLaunchKernelGGL(rank_pairs<true>, dim3((unsigned)blocks), dim3(TK_BLOCK), rank_smem(ldh, true), s, n_src, n_cand,
+                       n_count, (int)D, (int)ldh, (int)nc, (const float*)w.hs, (const float*)w.hd, w_out, b_out, target,
+                       (const float*)out_tlogit, f, gt, eq, nn);
+  else
+    hipLaunchKernelGGL(rank_pairs<false>, dim3((unsigned)blocks), dim3(TK_BLOCK), rank_smem(ldh, false), s, n_src,
+                       n_cand, n_count, (int)D, (int)ldh, (int)nc, (const float*)w.hs, (const float*)w.hd, w_out, b_out,
+                       target, (const float*)out_tlogit, f, gt, eq, nn);
+  TGNX_LAUNCH_CHECK("rank_pairs");
   return TGNX_OK;
 }
 

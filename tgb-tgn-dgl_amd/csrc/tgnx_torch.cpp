@@ -461,6 +461,43 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor
   return {val, idx, slot, logits, bad};
 }
 
+// where target[q] stands among the first n_count rows of z_cand (tgnx_link_predictor_rank):
+// (gt [B], eq [B], n [B] int64, tlogit [B])
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_rank(
+    const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src,
+    const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out,
+    const at::Tensor& target, int64_t n_count, const c10::optional<at::Tensor>& cand_key,
+    const c10::optional<at::Tensor>& src_key, const c10::optional<at::Tensor>& excl_ptr,
+    const c10::optional<at::Tensor>& excl_key) {
+  const auto [d_in, D] = topk_args(z_src, z_cand, w_src, w_dst, w_out, b_out, 1);
+  const int64_t B = z_src.size(0), C = z_cand.size(0);
+  TORCH_CHECK(n_count >= 0 && n_count <= C, "n_count must be in [0, n_cand], got ", n_count);
+  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
+  dev_tensor(target, at::kLong, "target");
+  TORCH_CHECK(target.numel() == B, "target must have n_src entries");
+  same_device(z_src, {&target});
+  const int64_t* ck = opt_long(cand_key, z_src, C, "cand_key");
+  const int64_t* sk = opt_long(src_key, z_src, B, "src_key");
+  const int64_t* ep = opt_long(excl_ptr, z_src, B + 1, "excl_ptr");
+  const int64_t* ek = opt_long(excl_key, z_src, -1, "excl_key");
+  TORCH_CHECK(!ep || excl_key.has_value(), "excl_ptr needs excl_key");
+  const int64_t nnz = excl_key.has_value() ? excl_key->numel() : 0;
+  const c10::OptionalDeviceGuard guard(z_src.device());
+  const auto lopt = z_src.options().dtype(at::kLong);
+  at::Tensor gt = at::empty({B}, lopt), eq = at::empty({B}, lopt), n = at::empty({B}, lopt);
+  at::Tensor tl = at::empty({B}, z_src.options());
+  const size_t nb = tgnx_link_predictor_rank_ws_bytes(B, C, d_in, D);
+  at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
+  check_rc(tgnx_link_predictor_rank(B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(),
+                                    w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(),
+                                    b_out.data_ptr<float>(), n_count, target.data_ptr<int64_t>(), ck, sk, ep, ek, nnz,
+                                    gt.data_ptr<int64_t>(), eq.data_ptr<int64_t>(), n.data_ptr<int64_t>(),
+                                    tl.data_ptr<float>(), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_link_predictor_rank");
+  return {gt, eq, n, tl};
+}
+
 void attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const c10::optional<at::Tensor>& e,
                const at::Tensor& indptr, int64_t heads) {
   dev_tensor(q, at::kFloat, "q");
@@ -926,6 +963,10 @@ TORCH_LIBRARY(tgnx, m) {
         "Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores, Tensor list_ptr, Tensor list_idx, "
         "int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
         &predictor_topk_lists);
+  m.def("predictor_rank(Tensor z_src, Tensor z_cand, Tensor w_src, Tensor? b_src, Tensor w_dst, Tensor? b_dst, "
+        "Tensor w_out, Tensor b_out, Tensor target, int n_count, Tensor? cand_key, Tensor? src_key, Tensor? excl_ptr, "
+        "Tensor? excl_key) -> (Tensor, Tensor, Tensor, Tensor)",
+        &predictor_rank);
   m.def("predictor_bwd(Tensor dout, Tensor z_src, Tensor z_dst, Tensor w_src, Tensor? b_src, Tensor w_dst, "
         "Tensor? b_dst, Tensor w_out, Tensor b_out, bool sigmoid, int[] need) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",

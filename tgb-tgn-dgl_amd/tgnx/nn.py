@@ -213,6 +213,13 @@ class LinkPredictor(nn.Module):
                              return_scores=return_scores, cand_key=cand_key, src_key=src_key, exclude=exclude,
                              lists=lists, validate=validate, max_len=max_len)
 
+    def rank(self, z_src, z_cand, target, **kw):
+        """Where z_cand[target[q]] stands for source q among the rows of z_cand: (rank [n_src] float64, gt, eq, n,
+        tlogit), ops.link_rank with its keywords (n_count, cand_key, src_key, exclude, validate) forwarded.  No
+        autograd."""
+        return ops.link_rank(z_src, z_cand, self.lin_src.weight, self.lin_src.bias, self.lin_dst.weight,
+                             self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, target, **kw)
+
 
 class TGNMemory(nn.Module):
     """modules/memory_module.py:25-215 over a device message store (csrc/tgnx_memstore.hip).

@@ -30,7 +30,7 @@ import torch
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "predictor_topk", "edge_attn_fwd", "edge_attn_bwd",
-       "predictor_topk_filtered", "predictor_topk_lists",
+       "predictor_topk_filtered", "predictor_topk_lists", "predictor_rank",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
@@ -235,6 +235,30 @@ def link_topk(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, k, sigmoi
         c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out), c(b_out), int(k), bool(sigmoid),
         bool(return_scores), key(cand_key), key(src_key), ptr, keys)
     return (val, idx, logits) if return_scores else (val, idx)
+
+
+@torch.no_grad()
+def link_rank(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, target, n_count=None, cand_key=None,
+              src_key=None, exclude=None, validate=True):
+    """Where source q's true destination z_cand[target[q]] stands among the first n_count rows of z_cand (default:
+    all) under LinkPredictor (tgnx_link_predictor_rank): no [n_src, n_cand] logits, no selection.  Returns
+    (rank float64 [n_src], gt, eq, n int64 [n_src], tlogit float32 [n_src]): with the keys and exclusions of
+    link_topk's filtered form, a candidate is compared when its key is not the target's, not src_key[q], not in q's
+    segment of exclude, and its logit is not NaN; gt / eq count the compared logits above / equal to the target's
+    (tlogit, the bits of link_topk's logits[q, target[q]]), n all of them, and rank = 1 + gt + eq / 2 (TGB's
+    convention).  The target is never excluded.  A target outside [0, n_cand) or a NaN tlogit: rank NaN, gt = eq = 0.
+    validate: the one host read link_topk makes for exclude.  Inference only: no autograd."""
+    c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+    dev, n_src = z_src.device, z_src.size(0)
+    key = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.long).contiguous().view(-1)  # noqa: E731
+    ptr = keys = None
+    if exclude is not None:
+        ptr, keys, _ = _ragged(exclude, n_src, dev, "exclude", validate, need_sorted=True)
+    gt, eq, n, tlogit = load().predictor_rank(
+        c(z_src), c(z_cand), c(w_src), c(b_src), c(w_dst), c(b_dst), c(w_out), c(b_out), key(target),
+        z_cand.size(0) if n_count is None else int(n_count), key(cand_key), key(src_key), ptr, keys)
+    rank = torch.add(gt, eq.double(), alpha=0.5).add_(1.0)
+    return rank.masked_fill_(torch.isnan(tlogit), float("nan")), gt, eq, n, tlogit
 
 
 class _TimeEncode(torch.autograd.Function):

@@ -474,7 +474,7 @@ class TgnEngine:
         self.plan_table = None
         self.use_plan_table = os.environ.get("TGNX_PLAN_TABLE", "1") != "0"
         self.dst_nodes = None if dst_nodes is None else torch.as_tensor(dst_nodes).to(self.dev, torch.long).contiguous()
-        self.seed, self.rank, self.world = int(seed), int(rank), int(world)
+        self.seed, self.dp_rank, self.world = int(seed), int(rank), int(world)
         # the data-parallel step forms (exchange collective, then the apply + Adam launch): world > 1, or forced at
         # world 1 (data_parallel=True), where the exchange over a 1-rank group is an identity and the step must
         # equal the world-1 one (tests/test_gpu_tgn_rccl.py runs it through RCCL)
@@ -543,7 +543,7 @@ class TgnEngine:
             self.comm[:G].copy_(model.grad_flat)
             model.grad_flat = self.comm[:G]          # the kernels' gradient buffer heads the exchange buffer
             self.xgather = self.comm[G:].view(self.world * self.xcap, rw)
-            self.xrows = self.xgather[self.rank * self.xcap:(self.rank + 1) * self.xcap]
+            self.xrows = self.xgather[self.dp_rank * self.xcap:(self.dp_rank + 1) * self.xcap]
 
     def ensure_neg(self, kn: int) -> None:
         """Grow the workspace for eval batches with kn negatives per event (TGB: ~999 on tgbl-wiki)."""
@@ -599,7 +599,7 @@ class TgnEngine:
 
     def advance(self, batch_start: int, B: int, train: bool):
         self._settle()
-        _lib.call("tgnx_tgnn_advance", _p(self.ctl), 0, batch_start, B, batch_start, 0, 0, 1, self.rank, self.world,
+        _lib.call("tgnx_tgnn_advance", _p(self.ctl), 0, batch_start, B, batch_start, 0, 0, 1, self.dp_rank, self.world,
                   self.seed, 1 if train else 0, self._stream())
 
     # ------------------------------------------------------------------ state
@@ -657,7 +657,7 @@ class TgnEngine:
         if self.exchange is not None:
             self.exchange(self.comm, False)
             return
-        exchange_collectives(self.comm, self.model.grad_flat.numel(), self.rank, self.world, self.exchange_mode)
+        exchange_collectives(self.comm, self.model.grad_flat.numel(), self.dp_rank, self.world, self.exchange_mode)
 
     def _apply_rows(self, b):
         _lib.call("tgnx_tgn_apply_rows", ctypes.byref(self.cfg), ctypes.byref(b), _p(self.xgather),
@@ -1099,6 +1099,54 @@ class TgnEngine:
                                   lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight, lp.lin_final.bias,
                                   sigmoid=True).view(-1)
 
+    @torch.no_grad()
+    def rank(self, src, dst, candidates=None, return_scores: bool = False, *, exclude_seen: bool = False,
+             exclude_self: bool = False, exclude=None):
+        """Where the model places the destination that happened: for every pair (src[i], dst[i]) the rank of dst[i]
+        among the candidates recommend() would choose from (default: the same), at the current stream state and
+        with recommend_filtered()'s exclusions (the "filtered" setting: the true destination itself is never
+        excluded, and its own node never competes with it, wherever it occurs among the candidates).  Returns
+        (rank [Q] float64 = 1 + gt + eq / 2, gt, eq, n [Q] int64, prob [Q][, logits [Q, C] unmasked]): gt / eq
+        candidates scored above / equal to the destination, n compared, prob the destination's link probability.
+        A destination outside `candidates` is ranked against all of them.  src, the candidates and dst are embedded
+        once with embed(); the counts come from one fused pass (ops.link_rank), no [Q, C] logits unless asked for.
+        Read-only as recommend() is."""
+        from . import ops
+        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        dst = torch.as_tensor(dst).to(self.dev, torch.long).contiguous().view(-1)
+        Q, N = src.numel(), self.cfg.num_nodes
+        if dst.numel() != Q:
+            raise ValueError(f"rank: {Q} sources for {dst.numel()} destinations")
+        if Q and bool(((src < 0) | (src >= N) | (dst < 0) | (dst >= N)).any()):
+            raise ValueError(f"rank: node ids must be in [0, {N})")
+        if candidates is None:
+            candidates = self.dst_nodes if self.dst_nodes is not None else torch.arange(N, device=self.dev)
+        cand = torch.as_tensor(candidates).to(self.dev, torch.long).contiguous().view(-1)
+        C = cand.numel()
+        ex = self._exclusions(src, exclude_seen, exclude)
+        z = self.embed(torch.cat([src, cand, dst]))
+        lp = self.model.link_pred
+        w = (lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight,
+             lp.lin_final.bias)
+        rank, gt, eq, n, tlogit = ops.link_rank(
+            z[:Q], z[Q:], *w, C + torch.arange(Q, device=self.dev), n_count=C, cand_key=torch.cat([cand, dst]),
+            src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2], validate=False)
+        out = (rank, gt, eq, n, torch.sigmoid(tlogit))
+        if return_scores:  # (over the same C + Q rows: the operands, and so the bits, of the counted logits)
+            out += (ops.link_topk(z[:Q], z[Q:], *w, 1, sigmoid=False, return_scores=True)[2][:, :C].contiguous(),)
+        return out
+
+    def rank_events(self, start: int, B: int, candidates=None, *, exclude_seen: bool = False,
+                    exclude_self: bool = False, exclude=None):
+        """One prequential step over resident rows [start, start + B): rank() of src[e] -> dst[e] at the state before
+        them, then observe(start, B).  Returns rank()'s tuple."""
+        start, B = int(start), int(B)
+        check_observe_args(start, B, self.cfg.max_batch, self.num_events, self.world)
+        out = self.rank(self._tab[0][start:start + B], self._tab[1][start:start + B], candidates,
+                        exclude_seen=exclude_seen, exclude_self=exclude_self, exclude=exclude)
+        self.observe(start, B)
+        return out
+
     # ------------------------------------------------------------------ resident eval pass
     def bind_eval_resident(self, split_lo: int, split_hi: int, batch: int, negs):
         """A validation / test pass over events [split_lo, split_hi) in batches of `batch`, resident on the device:
@@ -1141,7 +1189,7 @@ class TgnEngine:
         if self._ev is None:
             raise RuntimeError("TgnEngine: no eval pass bound (bind_eval_resident)")
         lo, hi, batch, Kn = self._ev
-        _lib.call("tgnx_tgn_eval_step_resident", ctypes.byref(self.cfg), self._ev_buf_ref, lo, hi, batch, Kn, self.rank,
+        _lib.call("tgnx_tgn_eval_step_resident", ctypes.byref(self.cfg), self._ev_buf_ref, lo, hi, batch, Kn, self.dp_rank,
                   self.world, self.seed, ctypes.c_void_p(self._ev_rr.data_ptr()), self._stream())
 
     def eval_resident_step(self):
@@ -1270,7 +1318,7 @@ class TgnEngine:
         par = self._parity if parity is None else parity
         if self._dp_pp():
             ap = self._apply_pending if apply is None else apply
-            rc = _lib.lib().tgnx_tgn_train_fwd_bwd_pp(self._cfg_ref, self._buf_ref, lo, hi, batch, self.rank, self.world,
+            rc = _lib.lib().tgnx_tgn_train_fwd_bwd_pp(self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world,
                                                      self.seed, self._res_drop, 1 if prefetched else 0, par,
                                                      1 if ap else 0, ctypes.c_void_p(self.xgather.data_ptr()),
                                                      ctypes.c_int64(self.xgather.shape[0]), st)
@@ -1282,13 +1330,13 @@ class TgnEngine:
                                                          self._res_drop, 1 if prefetched else 0, st)
         elif self._pipelined():
             f = _lib.lib().tgnx_tgn_train_fwd_bwd_split if self._split() else _lib.lib().tgnx_tgn_train_fwd_bwd_pipelined
-            rc = f(self._cfg_ref, self._buf_ref, lo, hi, batch, self.rank, self.world, self.seed, self._res_drop,
+            rc = f(self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world, self.seed, self._res_drop,
                    1 if prefetched else 0, st)
         elif self.fold_cursor:   # the batch cursor folded into the step's first launches
             f = _lib.lib().tgnx_tgn_train_step_resident if self._res_fused else _lib.lib().tgnx_tgn_train_fwd_bwd_resident
-            rc = f(self._cfg_ref, self._buf_ref, lo, hi, batch, self.rank, self.world, self.seed, self._res_drop, st)
+            rc = f(self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world, self.seed, self._res_drop, st)
         else:
-            rc = adv(self._ctl_p, 1, 0, 0, 0, lo, hi, batch, self.rank, self.world, self.seed, 1, st)
+            rc = adv(self._ctl_p, 1, 0, 0, 0, lo, hi, batch, self.dp_rank, self.world, self.seed, 1, st)
             rc |= fb(self._cfg_ref, self._buf_ref, 1, self._res_drop, st)
         if rc:
             raise RuntimeError(f"tgnx TGN resident step failed: {_lib.lib().tgnx_last_error().decode()}")
@@ -1311,7 +1359,7 @@ class TgnEngine:
         """The next batch's scan (split pipelined steps): rides beside the exchange."""
         if self._split():
             lo, hi, batch = self._res
-            _lib.call("tgnx_tgn_scan_next", self._cfg_ref, self._buf_ref, lo, hi, batch, self.rank, self.world, self.seed,
+            _lib.call("tgnx_tgn_scan_next", self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world, self.seed,
                       self._stream())
 
     def _allreduce(self, between=None):
@@ -1321,7 +1369,7 @@ class TgnEngine:
                 work = self.exchange(self.comm, True)
                 works = [] if work is None else [work]
             else:
-                works = exchange_collectives(self.comm, self.model.grad_flat.numel(), self.rank, self.world,
+                works = exchange_collectives(self.comm, self.model.grad_flat.numel(), self.dp_rank, self.world,
                                              self.exchange_mode, async_op=True)
             if between is not None:
                 between()

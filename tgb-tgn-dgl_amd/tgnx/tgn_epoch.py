@@ -217,6 +217,33 @@ def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclu
 
 
 @torch.no_grad()
+def rank_stream(model, neighbor_loader, lo, hi, batch, candidates=None, ks=(1, 10, 50), *, exclude_seen=False,
+                exclude_self=False):
+    """Prequential full-catalogue ranking over rows [lo, hi) of the event table of the engine train() / test()
+    attached to the model: every batch of `batch` events is ranked at the state before it (TgnEngine.rank_events: the
+    true destination against every candidate recommend() would choose from, recommend_filtered()'s exclusions), then
+    observed.  Returns {"mrr": mean 1 / rank, "hits@k": mean rank <= k for k in ks, "rank": float64 [hi - lo] on the
+    device}; skipped events (NaN rank) count as misses.  The means are taken on the device: one synchronisation, at the
+    end.  Switches the memory to eval first as recommend() does."""
+    eng = _bound_engine(model, neighbor_loader, "rank_stream")
+    lo, hi, batch = int(lo), int(hi), int(batch)
+    if not (0 <= lo <= hi <= eng.num_events) or not (0 < batch <= eng.cfg.max_batch):
+        raise ValueError(f"rank_stream: rows [{lo}, {hi}) batch {batch} outside the event table ({eng.num_events} "
+                         f"events) / max_batch ({eng.cfg.max_batch})")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    ranks = [eng.rank_events(a, min(batch, hi - a), candidates, exclude_seen=exclude_seen,
+                             exclude_self=exclude_self)[0] for a in range(lo, hi, batch)]
+    rank = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.float64, device=eng.dev)
+    stats = torch.stack([torch.nan_to_num(1.0 / rank, nan=0.0).sum()] + [(rank <= k).sum().double() for k in ks])
+    stats = (stats / max(hi - lo, 1)).tolist()
+    out = {"mrr": stats[0], "rank": rank}
+    out.update({f"hits@{k}": v for k, v in zip(ks, stats[1:])})
+    return out
+
+
+@torch.no_grad()
 def observe(model, neighbor_loader, src, dst, t, msg, batch=None):
     """Take new interactions into the stream state of the engine train() / test() attached to the model, without
     scoring them: the rows are appended to the resident event table, then memory, message stores and ring advance over
