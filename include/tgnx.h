@@ -593,6 +593,40 @@ int tgnx_tgn_compact_apply(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* b
                            int64_t* new_store, int64_t* kept, int64_t kept_len, const void* ws, size_t ws_bytes,
                            void* stream);
 
+/* Node-space growth (csrc/tgnx_grow.hip): move what cfg->num_nodes sizes into larger allocations, so
+ * that the result is bit for bit the state of an engine built at n_new nodes.  cfg / buf describe the engine as it
+ * is (num_nodes = N rows); nothing they point to is written.
+ * The new allocations (zero-filled by the caller is fine, not required: every word is written), all NULL-able in old /
+ * new pairs so that a loader or a model can grow on its own: */
+typedef struct {
+  int64_t *nbr, *eid;    /* [row_capacity, ring] */
+  float* rt;             /* [row_capacity, ring] */
+  int64_t* assoc;        /* [row_capacity] */
+  float* memory;         /* [row_capacity, mem_dim] */
+  int64_t* last_update;  /* [row_capacity] */
+  int32_t* node_gen;     /* [row_capacity] */
+  int64_t* store;        /* 4 * n_new + 2 * cfg->num_events int64 */
+} tgnx_tgn_grow_out;
+/* tgnx_tgn_grow_nodes (2 launches and an 8-byte memset): one kernel walks every row-major tensor — rows [0, N) are
+ * copied, rows [N, row_capacity) take what reset_state leaves (nbr / eid -1, rt -1.0f, assoc / memory / last_update /
+ * node_gen 0) — in 16-byte pieces where both pointers are 16-B aligned, 4-byte words otherwise; a second re-lays the
+ * store: the 4 * N node-table words, zero rows for nodes [N, n_new), then the 2 * cfg->num_events arena words, which
+ * move by 4 * (n_new - N) words as a block (run offsets are arena-relative: none is rewritten).  A tensor whose old
+ * and new pointer are both NULL is skipped; one of the two alone is TGNX_EINVAL.  row_capacity >= n_new >= N; rows
+ * beyond n_new are capacity the caller may hand out later without another call (the store has no such slack: its
+ * arena base is 4 * num_nodes words in, so it is re-laid for every new node count, tgnx_tgn_grow_store alone then).
+ * *bad (device int64, 8-B aligned; set by the call) counts the store runs {off, cnt} with cnt < 0, or cnt > 0 and
+ * not inside the arena words [0, 2 * cfg->num_events): they are counted, never followed — the caller reads it and
+ * keeps the old allocations when it is nonzero.  ctl is not touched: TGNX_CTL_GEN does not advance (new rows carry
+ * node_gen 0, which no generation equals once a step has run).  The workspace is not moved: its layout depends on
+ * num_nodes, the caller allocates tgnx_tgn_ws_bytes of the grown config, zero-filled.
+ * NULL cfg / buf / out / bad, n_new < N, row_capacity < n_new: TGNX_EINVAL, nothing launched; 2^31 nodes or more:
+ * TGNX_ETOOBIG.  One device only.  Test: tests/test_gpu_tgn_grow.py. */
+int tgnx_tgn_grow_nodes(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t n_new, int64_t row_capacity,
+                        const tgnx_tgn_grow_out* out, int64_t* bad, void* stream);
+int tgnx_tgn_grow_store(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t n_new, int64_t* new_store,
+                        int64_t* bad, void* stream);
+
 /* train(False): update the memory of every node from its stored messages, clear the stores
  * (memory_module.py:209-215).  Every row is computed from the pre-flush state (:212 updates arange(N) at
  * once).  Graphs with more nodes than the workspace's GRU row capacity run in chunks that read a snapshot

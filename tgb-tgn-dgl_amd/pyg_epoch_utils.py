@@ -3,3 +3,4 @@ step (tgnx/tgn_epoch.py; epoch_utils.train / test dispatch there for a TGN model
 from tgnx.tgn_epoch import compact, load_stream, observe, recommend, save_stream, test, train # noqa: F401
 from tgnx.tgn_epoch import recommend_filtered  # noqa: F401
 from tgnx.tgn_epoch import rank_stream  # noqa: F401
+from tgnx.tgn_epoch import grow_nodes, observe_grow  # noqa: F401

@@ -37,6 +37,46 @@ class LastNeighborLoader:
         _lib.call("tgnx_ring_reset", _lib.ptr(self.e_id), _lib.ptr(self.t), self.num_nodes, self.size,
                   _lib.stream(self.device))
 
+    @property
+    def node_capacity(self) -> int:
+        """Rows of the ring's allocations (neighbors / e_id / t / _assoc are their first num_nodes rows once grown)."""
+        alloc = getattr(self, "_alloc", None)
+        return self.num_nodes if alloc is None else int(alloc[0].shape[0])
+
+    def _install(self, nbr, e_id, t, assoc, num_nodes: int) -> None:
+        """Take allocations of >= num_nodes rows whose first rows hold the ring: the attributes become their first
+        num_nodes rows (contiguous views), version is bumped (an engine's prefetched batch is stale) and the sample
+        workspace, whose bitmap is sized by num_nodes, is dropped."""
+        n = int(num_nodes)
+        self._alloc = (nbr, e_id, t, assoc)
+        self.neighbors, self.e_id, self.t, self._assoc = nbr[:n], e_id[:n], t[:n], assoc[:n]
+        self.num_nodes = n
+        self.version += 1
+        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._ws_q = -1
+
+    def grow(self, num_nodes: int, capacity=None) -> int:
+        """Extend the ring to num_nodes rows in place of a rebuild: rows [0, N) are unchanged, the new rows are what
+        reset_state leaves (neighbors -1, e_id -1, t -1.0, _assoc 0).  num_nodes <= N is a no-op.  Rows come out of
+        the allocations' spare capacity when there is some, else everything moves into allocations of
+        max(num_nodes, capacity) rows (tgnx_tgn_grow_nodes).  Bumps version and drops the sample workspace.  A loader
+        bound to a TgnEngine is grown by the engine (TgnEngine.grow_nodes), which moves the model's tensors with it:
+        call this only on a loader used alone (__call__ / insert).  Returns num_nodes afterwards."""
+        from . import tgn
+        n, N = int(num_nodes), self.num_nodes
+        if n <= N:
+            return N
+        if n >= 1 << 31:
+            raise ValueError(f"LastNeighborLoader.grow: {n} nodes; node ids are below 2^31")
+        alloc = getattr(self, "_alloc", None) or (self.neighbors, self.e_id, self.t, self._assoc)
+        if n > alloc[0].shape[0]:
+            torch.cuda.synchronize(self.device)
+            old = dict(nbr=self.neighbors, eid=self.e_id, rt=self.t, assoc=self._assoc)
+            new = tgn.grow_node_tensors(self.device, N, n, max(n, int(capacity or 0)), self.size, 1, 1, old)
+            alloc = (new["nbr"], new["eid"], new["rt"], new["assoc"])
+        self._install(*alloc, n)
+        return n
+
     def _workspace(self, q: int) -> torch.Tensor:
         if q > self._ws_q:
             q2 = max(q, 2 * max(self._ws_q, 0), 1024)

@@ -60,6 +60,11 @@ class TgnBuffers(ctypes.Structure):
                 ("xcap", ctypes.c_int64), ("out_ev", P), ("plan_table", P), ("flags", ctypes.c_int32)]
 
 
+class TgnGrowOut(ctypes.Structure):      # tgnx_tgn_grow_out: the new allocations of tgnx_tgn_grow_nodes
+    _fields_ = [("nbr", P), ("eid", P), ("rt", P), ("assoc", P), ("memory", P), ("last_update", P), ("node_gen", P),
+                ("store", P)]
+
+
 # the memory modules' updater cell: TGNMemory.memory_updater (memory_module.py:70-78, memory_updater_cell
 # 'gru' | 'rnn') and DyRepMemory.memory_updater (:259-264, memory_updater_type) — the same state-dict names
 MEMORY_TYPES = ("tgn", "dyrep")
@@ -204,6 +209,49 @@ class TGNModel(nn.Module):
             self.store[:old.numel()].copy_(old)
 
     @property
+    def node_capacity(self) -> int:
+        """Rows of the allocations under memory / last_update / node_gen (they are the first num_nodes rows once the
+        node space has grown)."""
+        alloc = getattr(self, "_node_alloc", None)
+        return self.num_nodes if alloc is None else int(alloc[0].shape[0])
+
+    def _install_nodes(self, memory, last_update, node_gen, store, num_nodes: int) -> None:
+        """Take allocations of >= num_nodes rows whose first rows hold the state, and the store laid out for
+        num_nodes: the memory / last_update buffers are registered again as their first num_nodes rows (contiguous
+        views: state_dict() keeps the reference's names and [N, .] shapes), cfg.num_nodes follows."""
+        n = int(num_nodes)
+        self._node_alloc = (memory, last_update, node_gen)
+        self.memory.register_buffer("memory", memory[:n])
+        self.memory.register_buffer("last_update", last_update[:n])
+        self.node_gen = node_gen[:n]
+        self.store = store
+        self.cfg.num_nodes = n
+        self.num_nodes = n
+
+    def grow_nodes(self, n: int) -> int:
+        """Extend the node space to n nodes in place (n <= num_nodes: a no-op); returns num_nodes afterwards.  Rows
+        [0, N) of memory, last_update, node_gen and the stores are unchanged bit for bit, the new rows are what
+        reset_state leaves (zeros, empty store runs); no parameter moves.  With an engine bound the call goes through
+        it (TgnEngine.grow_nodes: the ring, the workspace and the bindings follow); a model on its own moves only its
+        own tensors (tgnx_tgn_grow_nodes) and its loader must be grown too (LastNeighborLoader.grow) before an engine
+        binds the pair."""
+        f = self._tgnx_grow() if getattr(self, "_tgnx_grow", None) is not None else None
+        if f is not None:
+            return f(n)
+        n, N = int(n), self.num_nodes
+        if not check_grow_args(N, n):
+            return N
+        dev = self.flat.device
+        torch.cuda.synchronize(dev)
+        rows = n > self.node_capacity
+        old = dict(memory=self.memory.memory, last_update=self.memory.last_update, node_gen=self.node_gen,
+                   store=self.store)
+        new = grow_node_tensors(dev, N, n, n, self.cfg.ring, self.D, self.cfg.num_events, old, rows=rows)
+        alloc = (new["memory"], new["last_update"], new["node_gen"]) if rows else self._node_alloc
+        self._install_nodes(*alloc, new["store"], n)
+        return n
+
+    @property
     def device(self):
         return self.flat.device
 
@@ -299,6 +347,88 @@ def grown_capacity(cap: int, need: int) -> int:
     return cap if need <= cap else max(need, cap + cap // 2)
 
 
+def grown_node_capacity(cap: int, need: int) -> int:
+    """Row capacity of the node tensors for `need` nodes when they hold `cap`: unchanged while they fit, else the
+    larger of `need` and 1.25 x cap — geometric, so n nodes added one at a time cost O(n) copied rows in all (about
+    5 n).  The factor is below the event table's 1.5: a node row (memory, three ring rows, five words) is several
+    times an event row, and capacity rows are allocated, initialised and never read."""
+    cap, need = int(cap), int(need)
+    if cap < 0 or need < 0:
+        raise ValueError(f"grown_node_capacity: negative node count ({cap}, {need})")
+    return cap if need <= cap else max(need, cap + cap // 4)
+
+
+MAX_NODES = 1 << 31    # node ids cross the C ABI checks as values below 2^31 (include/tgnx.h)
+
+
+def check_grow_args(num_nodes: int, n: int, world: int = 1, dp: bool = False) -> bool:
+    """Whether grow_nodes(n) has anything to do (n > num_nodes), or ValueError: one device, n below 2^31."""
+    if world > 1 or dp:
+        raise ValueError("grow_nodes: one device only (world > 1 / the data-parallel step forms are not built)")
+    n = int(n)
+    if n >= MAX_NODES:
+        raise ValueError(f"grow_nodes: {n} nodes; node ids are below 2^31")
+    return n > int(num_nodes)
+
+
+def check_append_args(validate: bool, grow: bool) -> None:
+    """ValueError for append_events(validate=False, grow=True): growing needs the host read validation makes."""
+    if grow and not validate:
+        raise ValueError("append_events: grow=True needs validate=True (the node space is sized from the one host "
+                         "read of the ids that validation makes)")
+
+
+# name in tgnx_tgn_buffers / tgnx_tgn_grow_out -> (trailing shape from (ring, mem_dim), dtype) of a [N, .] tensor
+NODE_ROW_TENSORS = {
+    "nbr": (lambda K, D: (K,), torch.long), "eid": (lambda K, D: (K,), torch.long),
+    "rt": (lambda K, D: (K,), torch.float32), "assoc": (lambda K, D: (), torch.long),
+    "memory": (lambda K, D: (D,), torch.float32), "last_update": (lambda K, D: (), torch.long),
+    "node_gen": (lambda K, D: (), torch.int32),
+}
+
+
+def grow_node_tensors(dev, N: int, n_new: int, cap: int, ring: int, mem_dim: int, num_events: int, old: dict,
+                      rows: bool = True) -> dict:
+    """tgnx_tgn_grow_nodes over the tensors in `old` (keys of NODE_ROW_TENSORS, each [N, .], and 'store'): returns
+    the new allocations by the same keys — row tensors of `cap` rows (rows [N, cap) as reset_state leaves them), the
+    store re-laid for n_new nodes over an arena of 2 * num_events words — after one host read of the device's count
+    of store runs outside the arena: RuntimeError if there is one, and the caller still holds the old tensors.
+    rows=False re-lays the store alone (tgnx_tgn_grow_store: growth inside the row capacity)."""
+    N, n_new, cap, K, D, nev = int(N), int(n_new), int(cap), int(ring), int(mem_dim), max(int(num_events), 1)
+    cfg = TgnConfig(num_nodes=N, num_events=nev, ring=K, mem_dim=D)
+    b, out, new = TgnBuffers(), TgnGrowOut(), {}
+    for k, (shape, dt) in NODE_ROW_TENSORS.items():
+        x = old.get(k)
+        if x is None or not rows:
+            continue
+        if tuple(x.shape) != (N,) + shape(K, D) or x.dtype != dt or not x.is_contiguous():
+            raise ValueError(f"grow_nodes: {k} is {tuple(x.shape)} {x.dtype}, expected contiguous "
+                             f"{(N,) + shape(K, D)} {dt}")
+        new[k] = torch.zeros((cap,) + shape(K, D), dtype=dt, device=dev)
+        setattr(b, k, x.data_ptr())
+        setattr(out, k, new[k].data_ptr())
+    st = old.get("store")
+    if st is not None and n_new > N:
+        if st.dtype != torch.long or st.numel() < 4 * N + 2 * nev or not st.is_contiguous():
+            raise ValueError(f"grow_nodes: the store holds {st.numel()} words, 4 * {N} + 2 * {nev} expected")
+        new["store"] = torch.zeros(4 * n_new + 2 * nev, dtype=torch.long, device=dev)
+        b.store, out.store = st.data_ptr(), new["store"].data_ptr()
+    if not new:
+        return new
+    bad = torch.zeros(1, dtype=torch.long, device=dev)
+    if rows:
+        _lib.call("tgnx_tgn_grow_nodes", ctypes.byref(cfg), ctypes.byref(b), n_new, cap, ctypes.byref(out), _p(bad),
+                  _lib.stream(dev))
+    else:
+        _lib.call("tgnx_tgn_grow_store", ctypes.byref(cfg), ctypes.byref(b), n_new, _p(new["store"]), _p(bad),
+                  _lib.stream(dev))
+    n_bad = int(bad.item())
+    if n_bad:
+        raise RuntimeError(f"grow_nodes: {n_bad} message-store runs outside the arena's {2 * nev} words; nothing was "
+                           "changed")
+    return new
+
+
 def check_event_rows(n_src: int, n_dst: int, n_t: int, msg_shape: tuple, msg_dim: int) -> int:
     """The row count of an appended chunk, or ValueError: src, dst, t of one length n and msg [n, msg_dim]."""
     n = int(n_src)
@@ -392,6 +522,21 @@ def check_stream_state(state, fingerprint: dict) -> int:
     return n
 
 
+def check_stream_state_grow(state, fingerprint: dict) -> tuple:
+    """check_stream_state for load_stream_state(grow=True): (num_events, the state's num_nodes), or ValueError.  The
+    state's num_nodes may differ from the engine's (>= 1, below 2^31) — more: the engine grows first, fewer: the rows
+    beyond are reset rows — and nothing else is relaxed: format, keys, ring / mem_dim / msg_dim and every shape, the
+    [N, .] ones by the state's own num_nodes."""
+    if not isinstance(state, dict) or "num_nodes" not in state:
+        return check_stream_state(state, fingerprint), int(fingerprint["num_nodes"])   # (raises: format / keys)
+    ns = int(state["num_nodes"])
+    if ns < 1 or ns >= MAX_NODES:
+        raise ValueError(f"load_stream_state: num_nodes = {ns}")
+    fp = dict(fingerprint)
+    fp["num_nodes"] = ns
+    return check_stream_state(state, fp), ns
+
+
 EXCHANGE_MODES = ("fused", "split")
 
 
@@ -436,7 +581,13 @@ class TgnEngine:
     A long-running stream (world 1): compact_events() retires the event rows that neither the ring nor a message
     store references and renumbers the rest in order, so the device footprint follows the live rows instead of the
     stream's length; stream_state() / load_stream_state() checkpoint the table, memory, stores, ring and ctl.  Both
-    drop the resident bindings, the plan table and the captured graphs: bind again in the new numbering."""
+    drop the resident bindings, the plan table and the captured graphs: bind again in the new numbering.
+
+    Nodes that first appear after the model was built (world 1): grow_nodes(n) / observe_events(..., grow=True) extend
+    the node space in place — memory, last_update, node_gen, the ring, the stores and the workspace move into larger
+    allocations (tgnx_tgn_grow_nodes), old rows bit for bit, new rows as reset_state leaves them — and cfg.num_nodes
+    stays the logical count over a row capacity (node_capacity, reserve_nodes).  Captured graphs are dropped, the
+    resident bindings are made again."""
 
     def __init__(self, model: TGNModel, loader, events: dict, optimizer: TgnAdam | None = None,
                  dst_nodes=None, seed: int = 0, rank: int = 0, world: int = 1, data_parallel: bool | None = None):
@@ -445,6 +596,7 @@ class TgnEngine:
         import weakref
         model._tgnx_finish = weakref.WeakMethod(self.finish)   # model.settle(): the deferred apply, if any
         model._tgnx_invalidate = weakref.WeakMethod(self.invalidate_prefetch)
+        model._tgnx_grow = weakref.WeakMethod(self.grow_nodes)   # model.grow_nodes(): the ring and bindings follow
         cfg = model.cfg
         if cfg.ring != loader.size:
             cfg.ring = loader.size
@@ -722,20 +874,123 @@ class TgnEngine:
         else:
             self._rebind_eval()
 
+    # ------------------------------------------------------------------ a node space that grows
+    @property
+    def node_capacity(self) -> int:
+        """Rows allocated under every [N, .] tensor (>= cfg.num_nodes, the logical node count; capacity rows are
+        reset rows no call reads: never candidates, never counted, not in stream_state())."""
+        return min(self.model.node_capacity, self.loader.node_capacity)
+
+    @torch.no_grad()
+    def _grow(self, n: int, cap: int) -> int:
+        """The node space at max(n, N) nodes over allocations of at least `cap` rows (grow_nodes / reserve_nodes)."""
+        m, ld, cfg = self.model, self.loader, self.cfg
+        N, have = int(cfg.num_nodes), self.node_capacity
+        n = max(int(n), N)
+        cap = max(int(cap), n, have)
+        if n == N and cap == have:
+            return N
+        if ld.num_nodes != N:
+            raise ValueError(f"grow_nodes: the loader holds {ld.num_nodes} nodes, the model {N}")
+        nb = 0
+        if cap < MAX_NODES:
+            probe = TgnConfig.from_buffer_copy(cfg)
+            probe.num_nodes = n
+            nb = int(_lib.lib().tgnx_tgn_ws_bytes(ctypes.byref(probe)))
+        if nb == 0:
+            raise ValueError(f"grow_nodes: {n} nodes (capacity {cap}) are beyond what the node id type and "
+                             "tgnx_tgn_ws_bytes accept")
+        self._settle()
+        torch.cuda.synchronize(self.dev)
+        old = dict(nbr=ld.neighbors, eid=ld.e_id, rt=ld.t, assoc=ld._assoc, memory=m.memory.memory,
+                   last_update=m.memory.last_update, node_gen=m.node_gen, store=m.store)
+        rows = cap > have
+        new = grow_node_tensors(self.dev, N, n, cap, cfg.ring, cfg.mem_dim, cfg.num_events, old, rows=rows)
+        # (a store run outside the arena has raised by now, with nothing swapped)
+        if rows:
+            ring, node = tuple(new[k] for k in ("nbr", "eid", "rt", "assoc")), \
+                tuple(new[k] for k in ("memory", "last_update", "node_gen"))
+        else:
+            ring, node = ld._alloc, m._node_alloc
+        ld._install(*ring, n)
+        m._install_nodes(*node, new.get("store", m.store), n)
+        if n > N:   # the workspace's layout follows num_nodes: a fresh one (scratch only: zero = initial state)
+            self.ws = torch.zeros(nb, dtype=torch.uint8, device=self.dev)
+        self._prefetched = False
+        self._graphs = None                                   # captured pointers (and the captured N) are stale
+        self._group = None
+        for a in ("_pending", "_keep"):
+            self.__dict__.pop(a, None)
+        if hasattr(self, "_res_buf"):
+            self.bind_resident(*self._res, dropout=bool(self._res_drop))   # (drops and rebuilds the plan table)
+        else:
+            self._release_plan_table()
+            self._rebind_eval()
+        return n
+
+    def reserve_nodes(self, cap: int) -> None:
+        """Row capacity for at least cap nodes ahead of time (append_events(grow=True) grows it geometrically
+        otherwise): the [N, .] tensors move into allocations of cap rows, cfg.num_nodes stays.  Pointers change, so
+        graphs and bindings are treated as grow_nodes treats them."""
+        check_grow_args(self.cfg.num_nodes, cap, self.world, self.dp)
+        self._grow(self.cfg.num_nodes, cap)
+
+    def grow_nodes(self, n: int) -> int:
+        """Extend the node space to n nodes in place; returns cfg.num_nodes afterwards (n <= N: a no-op returning N).
+        The result is bit for bit the state of an engine built at n nodes and fed the same calls: rows [0, N) of
+        memory, last_update, node_gen, the ring (neighbors, e_id, t, _assoc), the store's node table and every arena
+        entry are unchanged; rows [N, n) are what reset_state leaves on a fresh engine (memory 0, last_update 0,
+        node_gen 0, neighbors -1, e_id -1, t -1.0, empty store runs); no parameter, Adam moment, ctl word (GEN and
+        ERR included) or event row changes.  The tensors move into allocations of node_capacity >= n rows when the
+        capacity is exceeded (tgnx_tgn_grow_nodes), the store is re-laid for every growth (its arena sits 4 * N
+        words in), and the workspace is a fresh zero one.  Everything that captured a pointer is dropped as
+        reserve_events / ensure_neg drop it: the captured train and eval graphs, the plan table, the prefetched
+        batch; the resident train and eval bindings are made again (their rows still exist; the eval cursor and its
+        reciprocal ranks are kept), so capture again and go on.  loader.version is bumped.
+        Every default that means "all nodes" (recommend / rank candidates, embed's id check, the train negatives'
+        range without dst_nodes) follows cfg.num_nodes.  A dst_nodes the caller passed is NOT extended: the train
+        negative pool and the default candidates are the caller's statement.
+        n beyond what the id type and tgnx_tgn_ws_bytes accept: ValueError before anything is touched; a store run
+        outside the arena: RuntimeError, the engine untouched.  One device only (ValueError at world > 1 / dp).
+        One host read."""
+        if not check_grow_args(self.cfg.num_nodes, n, self.world, self.dp):
+            return int(self.cfg.num_nodes)
+        return self._grow(n, n)
+
     @torch.no_grad()
     def append_events(self, src, dst, t, msg, validate: bool = True):
         """Append rows to the device event table; returns (start, n): they are rows [start, start + n).  dtypes are
         converted as the constructor converts them; msg must be [n, msg_dim].  validate: one host read checks the
         node ids against [0, N) and raises ValueError before anything is written; without it (no host read) ids are
         clamped into [0, N), so an id out of range never reaches a kernel as an index.  Appending alone moves no
-        stream state: observe() / observe_range() / eval and train batches over the new rows do."""
+        stream state: observe() / observe_range() / eval and train batches over the new rows do.  Ids of nodes that
+        do not exist yet: append_events_grow()."""
+        return self._append(src, dst, t, msg, validate, False)
+
+    @torch.no_grad()
+    def append_events_grow(self, src, dst, t, msg):
+        """append_events for rows that may name new nodes: an id >= N is not an error — the host read that validation
+        makes takes the largest id instead (one device min / max over src and dst) and the node space grows to it + 1
+        first (grow_nodes semantics, capacity by grown_node_capacity).  Negative ids are still a ValueError."""
+        return self._append(src, dst, t, msg, True, True)
+
+    def _append(self, src, dst, t, msg, validate: bool, grow: bool):
+        check_append_args(validate, grow)
         src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
         dst = torch.as_tensor(dst).to(self.dev, torch.long).contiguous().view(-1)
         t = torch.as_tensor(t).to(self.dev, torch.float32).contiguous().view(-1)
         msg = torch.as_tensor(msg).to(self.dev, torch.float32).contiguous()
         n = check_event_rows(src.numel(), dst.numel(), t.numel(), tuple(msg.shape), self.cfg.msg_dim)
         N = self.cfg.num_nodes
-        if validate:
+        if grow:
+            check_grow_args(N, N, self.world, self.dp)
+            if n:
+                lo, hi = torch.stack([torch.minimum(src.min(), dst.min()), torch.maximum(src.max(), dst.max())]).tolist()
+                if lo < 0:
+                    raise ValueError("append_events: node ids must not be negative")
+                if hi >= N:
+                    self._grow(hi + 1, grown_node_capacity(self.node_capacity, hi + 1))
+        elif validate:
             if n and bool(((src < 0) | (src >= N) | (dst < 0) | (dst >= N)).any()):
                 raise ValueError(f"append_events: node ids must be in [0, {N})")
         else:
@@ -774,12 +1029,14 @@ class TgnEngine:
         for a in range(lo, hi, batch):
             self.observe(a, min(batch, hi - a))
 
-    def observe_events(self, src, dst, t, msg, batch=None, validate: bool = True):
+    def observe_events(self, src, dst, t, msg, batch=None, validate: bool = True, grow: bool = False):
         """append_events, then observe the new rows in batches of `batch` (default cfg.max_batch) — batched per call:
-        two calls of 30 events at batch 50 are two batches of 30.  Returns (start, n)."""
+        two calls of 30 events at batch 50 are two batches of 30.  grow: nodes that first appear in these rows are
+        admitted (append_events_grow; grow without validate is a ValueError: growing needs validation's host read).
+        Returns (start, n)."""
         if self.world > 1:
             raise ValueError("observe_events: one device only (world > 1 is not built)")
-        start, n = self.append_events(src, dst, t, msg, validate=validate)
+        start, n = self._append(src, dst, t, msg, validate, grow)
         self.observe_range(start, start + n, batch)
         return start, n
 
@@ -904,13 +1161,29 @@ class TgnEngine:
         """Make a stream_state() dict this engine's stream state, whatever table the engine was built over (one row
         is enough).  format, the fingerprint, the shapes and ERR == 0 in the saved ctl are checked first: ValueError
         before anything is written.  Table and store are sized by reserve_events, everything is copied in,
-        loader.cur_e_id = num_events, and bindings and graphs are dropped as compact_events drops them."""
+        loader.cur_e_id = num_events, and bindings and graphs are dropped as compact_events drops them.  A state of
+        another node count: load_stream_state_grow()."""
+        self._load_stream_state(state, False)
+
+    @torch.no_grad()
+    def load_stream_state_grow(self, state: dict) -> None:
+        """load_stream_state for a state whose num_nodes may differ from the engine's (check_stream_state_grow: nothing
+        else is relaxed).  A state of more nodes grows the engine first (grow_nodes); a state of fewer nodes is loaded
+        into the first rows and the engine's other rows become reset rows (as grow_nodes would have left them)."""
+        self._load_stream_state(state, True)
+
+    def _load_stream_state(self, state: dict, grow: bool) -> None:
         if self.world > 1:
             raise ValueError("load_stream_state: one device only (world > 1 is not built)")
-        n = check_stream_state(state, stream_fingerprint(self.cfg))
+        if grow:
+            n, ns = check_stream_state_grow(state, stream_fingerprint(self.cfg))
+        else:
+            n, ns = check_stream_state(state, stream_fingerprint(self.cfg)), int(self.cfg.num_nodes)
         err = int(state["ctl"][11])
         if err:
             raise ValueError(f"load_stream_state: the saved ctl block carries step error flags {err:#x}")
+        if ns > self.cfg.num_nodes:
+            self.grow_nodes(ns)
         self.finish()
         self._drop_bindings()
         self.reserve_events(max(n, 1))
@@ -919,11 +1192,15 @@ class TgnEngine:
             buf[:n].copy_(state[k].to(self.dev, buf.dtype))
         self._set_rows(n)
         m, ld, N = self.model, self.loader, self.cfg.num_nodes
-        m.store[:4 * N].copy_(state["store_nodes"].to(self.dev, torch.long).reshape(-1))
+        m.store[:4 * ns].copy_(state["store_nodes"].to(self.dev, torch.long).reshape(-1))
+        m.store[4 * ns:4 * N].zero_()                       # (ns < N: empty runs for the nodes the state lacks)
         m.store[4 * N:4 * N + 2 * n].copy_(state["store_arena"].to(self.dev, torch.long))
-        for dst, k in ((m.memory.memory, "memory"), (m.memory.last_update, "last_update"), (m.node_gen, "node_gen"),
-                       (ld.neighbors, "neighbors"), (ld.e_id, "e_id"), (ld.t, "ring_t"), (self.ctl, "ctl")):
-            dst.copy_(state[k].to(self.dev, dst.dtype))
+        for dst, k, reset in ((m.memory.memory, "memory", 0), (m.memory.last_update, "last_update", 0),
+                              (m.node_gen, "node_gen", 0), (ld.neighbors, "neighbors", -1), (ld.e_id, "e_id", -1),
+                              (ld.t, "ring_t", -1.0)):
+            dst[:ns].copy_(state[k].to(self.dev, dst.dtype))
+            dst[ns:].fill_(reset)
+        self.ctl.copy_(state["ctl"].to(self.dev, self.ctl.dtype))
         ld.cur_e_id = n
         ld.version = getattr(ld, "version", 0) + 1
 

@@ -23,6 +23,8 @@ updates the stores, the memory and the ring in eval order.
   observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
       table and taken into memory, stores and ring as test() batches would leave them, without negatives or scores
       (TgnEngine.observe_events)
+  grow_nodes(model, neighbor_loader, n) -> num_nodes: the node space extended in place for nodes that first appear
+      after the model was built (TgnEngine.grow_nodes); observe_grow(...) is observe() that does it from the ids it is given
   compact(model, neighbor_loader, upto=None, capacity=None) -> kept: retire the event-table rows nothing references
       and renumber the rest in order (TgnEngine.compact_events); kept[new] = old
   save_stream(model, neighbor_loader, f) / load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
@@ -249,7 +251,20 @@ def observe(model, neighbor_loader, src, dst, t, msg, batch=None):
     scoring them: the rows are appended to the resident event table, then memory, message stores and ring advance over
     them in batches of `batch` (default: the model's max_batch) exactly as test() batches would leave them
     (TgnEngine.observe_events; no negatives, no outputs).  Straight after train() the memory is switched to eval first,
-    as test() and recommend() do.  Returns (start, n): the events are rows [start, start + n) of the table."""
+    as test() and recommend() do.  Returns (start, n): the events are rows [start, start + n) of the table.  Rows that
+    may name new nodes: observe_grow()."""
+    return _observe(model, neighbor_loader, src, dst, t, msg, batch, False)
+
+
+@torch.no_grad()
+def observe_grow(model, neighbor_loader, src, dst, t, msg, batch=None):
+    """observe() for interactions that may name nodes the model has not seen: node ids at or above its num_nodes are
+    admitted — the node space grows to the largest id + 1 first (TgnEngine.grow_nodes; train() / test() capture their
+    graphs again on their next call)."""
+    return _observe(model, neighbor_loader, src, dst, t, msg, batch, True)
+
+
+def _observe(model, neighbor_loader, src, dst, t, msg, batch, grow):
     eng = getattr(_owner(model), "_tgnx_engine", None)
     if eng is None or eng.loader is not neighbor_loader:
         raise RuntimeError("tgnx observe: no engine bound to this model / neighbor_loader yet (run train() or test() "
@@ -257,7 +272,7 @@ def observe(model, neighbor_loader, src, dst, t, msg, batch=None):
     if eng._mode_train:
         eng.flush()
         eng._mode_train = False
-    start, n = eng.observe_events(src, dst, t, msg, batch=batch)
+    start, n = eng.observe_events(src, dst, t, msg, batch=batch, grow=grow)
     neighbor_loader.cur_e_id = start + n
     return start, n
 
@@ -268,6 +283,22 @@ def _bound_engine(model, neighbor_loader, what):
         raise RuntimeError(f"tgnx {what}: no engine bound to this model / neighbor_loader yet (run train() or test() "
                            "first: they bind the event table)")
     return eng
+
+
+@torch.no_grad()
+def grow_nodes(model, neighbor_loader, n):
+    """Extend the node space of the model, its neighbor_loader and the engine train() / test() attached to them to n
+    nodes in place (TgnEngine.grow_nodes): old rows unchanged, new rows as reset_state leaves them, no parameter
+    touched.  Before an engine exists the model and the loader are grown on their own.  Returns num_nodes afterwards.
+    The engine's dst_nodes (the train negative pool) is not extended."""
+    m = _owner(model)
+    eng = getattr(m, "_tgnx_engine", None)
+    if eng is not None and eng.loader is neighbor_loader:
+        return eng.grow_nodes(n)
+    if getattr(m, "_tgnx_grow", None) is not None and m._tgnx_grow() is not None:
+        raise RuntimeError("tgnx grow_nodes: the model is bound to an engine over another neighbor_loader")
+    neighbor_loader.grow(n)
+    return m.grow_nodes(n)
 
 
 @torch.no_grad()
