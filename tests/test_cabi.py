@@ -62,3 +62,32 @@ def test_torch_ops_library_registers_every_op():
     src, dst = rng.integers(0, 50, 600), rng.integers(0, 50, 600)
     got = ns.block_ids(torch.from_numpy(src), torch.from_numpy(dst), 200).numpy()
     assert np.array_equal(got, blocks_ref.block_ids(src, dst, 200))
+
+
+def test_tgn_param_layout_refuses_widths_outside_the_domain():
+    """check_cfg accepts every even mem_dim in [2, 128]; 0, an odd width, 130 and a negative one are refused with its
+    message (tgnx_tgn_param_layout only computes offsets: no device), and a valid width afterwards is laid out as
+    tgnx.tgn.param_shapes says.  tests/test_gpu_tgn_mem_dims.py compares the accepted range with the oracle."""
+    from tgnx import _lib
+    from tgnx.tgn import PARAM_ORDER, TgnConfig, param_shapes
+    L = _lib.lib()
+
+    def layout(D):
+        cfg = TgnConfig(num_nodes=300, num_events=100, ring=10, mem_dim=D, msg_dim=16, heads=2, max_batch=50, max_neg=1,
+                        aggr=0, dropout=0.0, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, layers=1, updater=0, emb_in_msg=0)
+        off = (ctypes.c_int64 * (len(PARAM_ORDER) + 1))()
+        return L.tgnx_tgn_param_layout(ctypes.byref(cfg), off), list(off)
+
+    for D in (0, 7, 130, -2):
+        rc, _ = layout(D)
+        assert rc == -1, D                                                 # TGNX_EINVAL
+        assert b"tgn: mem_dim must be even and <= 128" in L.tgnx_last_error(), D
+    for D in (2, 6, 128):                                                  # the domain's ends, after the refusals
+        rc, off = layout(D)
+        assert rc == 0, D
+        shapes = param_shapes(D, 16)
+        blocks = sorted((o, o + int(np.prod(shapes[name])), name) for name, o in zip(PARAM_ORDER, off))
+        assert blocks[0][0] == 0 and blocks[-1][1] <= off[-1], (D, blocks, off[-1])
+        for (a0, a1, name), (b0, _, _) in zip(blocks, blocks[1:]):
+            assert a1 <= b0, (D, name)                                     # no two tensors overlap
+        assert all(a % 4 == 0 for a, _, _ in blocks), (D, blocks)          # every block starts 16-byte aligned

@@ -290,9 +290,15 @@ def test_tgn_pipelined_equals_resident(layers, updater, emb, pp, table):
     engine has drawn the next batch's too), outputs, parameters and memory within the fused-Adam tolerances
     (resynchronised per step).  table: the parity-set step reads the split's plans from the table built at
     binding (tgnx_tgn_plan_table) instead of its scan's, which then only walks the node sets."""
+    pipelined_equals_resident(layers, updater, emb, pp, table)
+
+
+def pipelined_equals_resident(layers, updater, emb, pp, table, D=32):
+    """The comparison of test_tgn_pipelined_equals_resident at memory width D (test_gpu_tgn_mem_dims.py runs it at
+    the edge widths)."""
     engines = []
     for pipe in (True, False):
-        s, ref, opt_ref, lref, model, opt, eng = _setup("last", layers=layers, updater=updater,
+        s, ref, opt_ref, lref, model, opt, eng = _setup("last", D=D, layers=layers, updater=updater,
                                                         memory="dyrep" if any(emb) else "tgn", emb=emb)
         model.cfg.dropout = 0.1
         eng.pipeline = pipe

@@ -147,10 +147,13 @@ def _assert_twins(a, b, skip_ctl=()):
     return sa
 
 
-def _ptrs(e):
+def _bufs(e):
     m, ld = e.model, e.loader
-    return tuple(x.data_ptr() for x in (m.memory.memory, m.memory.last_update, m.node_gen, m.store, ld.neighbors,
-                                        ld.e_id, ld.t, ld._assoc, e.ws))
+    return (m.memory.memory, m.memory.last_update, m.node_gen, m.store, ld.neighbors, ld.e_id, ld.t, ld._assoc, e.ws)
+
+
+def _ptrs(e):
+    return tuple(x.data_ptr() for x in _bufs(e))
 
 
 def _pair(ev, n0, n1, split, **kw):
@@ -315,10 +318,12 @@ def test_tiny_graph_below_two_batches(form):
 def test_never_observed_and_two_growths_in_a_row():
     ev, n0 = _stream(), _n0()
     small, twin = _pair(ev, n0, N1, HALF)
-    p0 = _ptrs(small)
+    held, p0 = _bufs(small), _ptrs(small)    # (the first allocations stay alive: the allocator may otherwise hand their
+                                             # addresses, free after the first growth, to the second growth's tensors)
     assert small.grow_nodes(n0 + 7) == n0 + 7                             # nothing observed yet
     assert small.grow_nodes(N1) == N1                                     # and again, no call between
     assert all(a != b for a, b in zip(_ptrs(small), p0))
+    del held
     _assert_twins(small, twin)
     for e in (small, twin):
         e.observe_range(0, HALF, B)

@@ -33,6 +33,8 @@ import numpy as np
 import pytest
 import torch
 
+from tgn_oracle_steps import oracle_embed as _oracle_embed  # (the oracle's eval forward for a node set)
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 N, d, D, B, KN, NEV = 300, 16, 32, 50, 5, 600
@@ -96,20 +98,6 @@ def _oracle_state(ref, s, negs, batch, count):
         sl = slice(st * batch, (st + 1) * batch)
         eval_step(ref, lref, ev_t, ev_msg, src[sl], dst[sl], negs[sl], ev_t[sl], ev_msg[sl])
     return lref, ev_t, ev_msg
-
-
-@torch.no_grad()
-def _oracle_embed(ref, lref, ev_t, ev_msg, nodes):
-    """The oracle's eval forward for a node set (oracle/tgn_ref.py eval_step, up to the embeddings)."""
-    from oracle.tgn_ref import sample_hops
-    ref.eval()
-    nodes = torch.as_tensor(nodes, dtype=torch.long)
-    n_id, ei, e_id = sample_hops(ref, lref, nodes.unique().numpy())
-    assoc = torch.zeros(N, dtype=torch.long)
-    assoc[n_id] = torch.arange(n_id.size(0))
-    z, last_update = ref.memory(n_id)
-    z = ref.gnn(z, last_update, ei, ev_t[e_id], ev_msg[e_id])
-    return z[assoc[nodes]]
 
 
 def _query_nodes(s, events):

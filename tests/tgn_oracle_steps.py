@@ -20,6 +20,20 @@ def rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-12))
 
 
+@torch.no_grad()
+def oracle_embed(ref, lref, ev_t, ev_msg, nodes):
+    """The oracle's eval forward for a node set (oracle/tgn_ref.py eval_step, up to the embeddings)."""
+    from oracle.tgn_ref import sample_hops
+    ref.eval()
+    nodes = torch.as_tensor(nodes, dtype=torch.long)
+    n_id, ei, e_id = sample_hops(ref, lref, nodes.unique().numpy())
+    assoc = torch.zeros(ref.memory.memory.size(0), dtype=torch.long)
+    assoc[n_id] = torch.arange(n_id.size(0))
+    z, last_update = ref.memory(n_id)
+    z = ref.gnn(z, last_update, ei, ev_t[e_id], ev_msg[e_id])
+    return z[assoc[nodes]]
+
+
 class Rig:
     """A RefTGN and a TgnEngine over one synthetic stream, from identical parameters.  The oracle is built with
     dropout 0: its only dropout is the mask a test injects (RefTransformerConv.keep)."""
@@ -73,6 +87,10 @@ class Rig:
                     opt.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
             model.memory.memory.copy_(self.ref.memory.memory)
             model.memory.last_update.copy_(self.ref.memory.last_update)
+
+    def oracle_embed(self, nodes):
+        """The oracle's eval-mode embeddings of `nodes` at its current state; changes no state."""
+        return oracle_embed(self.ref, self.lref, self.ev_t, self.ev_msg, nodes)
 
     def _note(self, key, v):
         self.worst[key] = max(self.worst.get(key, 0.0), float(v))

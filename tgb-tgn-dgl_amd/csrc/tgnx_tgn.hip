@@ -2774,7 +2774,8 @@ __host__ __device__ inline int evs_stride(int D) { return 7 * D + 8; }
 // (Read from global memory directly, the forward's W[o][k] with lanes over o touched 64 cache lines per
 // load instruction.)
 __host__ __device__ inline size_t tgn_pred_smem(int D) { return (size_t)2 * D * (D + 1) * sizeof(float); }
-constexpr int PRED_SU = 16;  // float4 per staging thread per matrix per round (D <= 110: one round)
+constexpr int PRED_SU = 16;  // float4 per staging thread per matrix per round (2 hops, 192 staging threads: D <= 110 is
+                             // one round, 112 .. 128 two; 1 hop, 320: always one)
 // nmk > 0 (pipelined resident step): the last nmk blocks mark the NEXT batch instead (mark_body, ahead 1):
 // the ring insert of this batch ran beside the GRU, and nothing of this step reads what marking writes.
 // ATT (1-hop train): the TransformerConv forward of the event's three roots runs here too — waves 1-3 one
