@@ -7,11 +7,13 @@ restatement on those logits.  Against the oracle (RefLinkPredictor over all pair
 rounding: with tol = 2e-5, scale = max(|ref|, 1) and r the reference logits over the compared set,
 #{r > r_t + 2 tol scale} <= gt and gt + eq <= #{r >= r_t - 2 tol scale}.  So that this is not vacuous the two bounds
 coincide on the reference alone for at least 9 in 10 rows that are neither tied on purpose nor skipped; the shares
-observed on the CPU with the seeds below: 1x1 1/1, 17x257 12/12, 70x600 58/59, 5x3000 3/3 (asserted again here).
+observed on the CPU with the seeds below: 1x1 1/1, 17x257 12/12, 70x600 58/59, 5x3000 3/3, 3x300 2/2 (asserted again
+here).
 
 Shapes (n_src, n_cand, d_in, D), from test_gpu_topk_filter.py: the smallest; two source tiles, one partial, and a
 chunk boundary (the chunk is 256); D no multiple of 4; many chunks and an exclusion list of 3,000 keys (past the
-1,024-key LDS staging).  Every shape runs with n_count = n_cand and with n_count = n_cand - 3 (targets in rows past
+1,024-key LDS staging); D = 3, a row of one 16-byte vector, shorter than the pair loop's load group (the seed is one
+at which the +inf entry meets weights of both signs, so that its column is NaN at D = 3 as well).  Every shape runs with n_count = n_cand and with n_count = n_cand - 3 (targets in rows past
 n_count).  Targets, by source: 0, 255 (the last position of a chunk), 256 (the first of the next), -1 (skipped),
 n_cand - 1, n_cand (skipped), n_cand - 2, n_cand - 4, then random.  Sources q = 0 mod 8 (no exclusions) get two exact
 copies of their target's z_cand row: one under another key (it must land in eq), one under the target's key (in no
@@ -37,9 +39,9 @@ K = 10
 NANPOS, INFPOS = 5, 6
 
 #        n_src, n_cand, d_in, D
-CASES = [(1, 1, 100, 100), (17, 257, 100, 100), (70, 600, 30, 30), (5, 3000, 32, 32)]
+CASES = [(1, 1, 100, 100), (17, 257, 100, 100), (70, 600, 30, 30), (5, 3000, 32, 32), (3, 300, 5, 3)]
 IDS = ["x".join(map(str, c)) for c in CASES]
-SEEDS = {CASES[0]: 2, CASES[1]: 274, CASES[2]: 670, CASES[3]: 3005}
+SEEDS = {CASES[0]: 2, CASES[1]: 274, CASES[2]: 670, CASES[3]: 3005, CASES[4]: 313}
 
 
 def _inputs(case):
@@ -174,8 +176,8 @@ def test_counts_are_the_reference_on_those_logits(cases, case):
                 assert rank[q] == 1.0 or not 0 <= c["target"][q] < n_cand
     if c["big"]:
         assert c["target"][2] == LCHUNK and c["rank"][n_cand][0][2] == 1.0 and not np.isnan(c["rank"][n_cand][4][2].item())
-        q = 4                                                     # a target past n_count is ranked against all n_count
-        assert c["target"][q] == n_cand - 1 and c["rank"][n_cand - 3][3][q] > 0
+        if n_src > 4:                                             # a target past n_count is ranked against all n_count
+            assert c["target"][4] == n_cand - 1 and c["rank"][n_cand - 3][3][4] > 0
 
 
 @pytest.mark.parametrize("case", CASES[1:], ids=IDS[1:])

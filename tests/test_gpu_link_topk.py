@@ -14,7 +14,8 @@ lin_final(relu(lin_src(zs)[:, None] + lin_dst(zc)[None])).  Per case:
   * sigmoid=True returns the sigmoid of the same selection.
 Shapes: one pair; fewer candidates than k (padding); more than one source tile and a partial one, a partial chunk;
 200 x 1000 (the 512-candidate chunks are not reached below 256 workgroups: 13 tiles x 20 chunks does, at 10,000
-candidates — `test_wide_chunks`); k = 128 = TGNX_TOPK_MAX over 12 chunks; d_in != D; D no multiple of 4."""
+candidates — `test_wide_chunks`); k = 128 = TGNX_TOPK_MAX over 12 chunks; d_in != D; D no multiple of 4; D = 3 (a
+row of one 16-byte vector: shorter than the pair loop's load group)."""
 import numpy as np
 import pytest
 import torch
@@ -25,7 +26,7 @@ TOL = 2e-5
 
 #        n_src, n_cand, d_in, D, k
 CASES = [(1, 1, 100, 100, 1), (3, 5, 100, 100, 10), (70, 257, 100, 100, 10), (200, 1000, 100, 100, 64),
-         (5, 3000, 32, 32, 128), (4, 300, 48, 100, 7), (17, 600, 30, 30, 5)]
+         (5, 3000, 32, 32, 128), (4, 300, 48, 100, 7), (17, 600, 30, 30, 5), (3, 300, 5, 3, 2)]
 
 
 def _weights(d_in, D, seed):

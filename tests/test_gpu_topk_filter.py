@@ -9,7 +9,7 @@ third check: with tol = 2e-5 and scale = max(|ref|, 1), every selected candidate
 reference's k-th largest OF THE ALLOWED SET - 2 tol scale, and the values are within tol scale.
 
 Shapes (n_src, n_cand, d_in, D, k): the smallest; two source tiles, one partial, and a chunk boundary; D no multiple
-of 4; k = 128 over 12 chunks.  Exclusion lists per source, by q mod 4: none; a few keys that hit the first and last
+of 4; k = 128 over 12 chunks; D = 3 (a row shorter than the pair loop's load group).  Exclusion lists per source, by q mod 4: none; a few keys that hit the first and last
 position of a chunk, the last candidate and nothing at all; every candidate (the row is padding; 3,000 keys: past
 the LDS staging, searched in global memory); all but a few (k larger than what remains).  cand_key carries a
 duplicated node.  List lengths 0, 1, one chunk (256), one chunk + 1, and 3,000 at k = 128; entries -1, entries >=
@@ -26,7 +26,8 @@ TOL = 2e-5
 LCHUNK = 256
 
 #        n_src, n_cand, d_in, D, k
-CASES = [(1, 1, 100, 100, 1), (17, 257, 100, 100, 10), (70, 600, 30, 30, 5), (5, 3000, 32, 32, 128)]
+CASES = [(1, 1, 100, 100, 1), (17, 257, 100, 100, 10), (70, 600, 30, 30, 5), (5, 3000, 32, 32, 128),
+         (3, 300, 5, 3, 2)]
 IDS = ["x".join(map(str, c)) for c in CASES]
 
 

@@ -26,17 +26,26 @@
 // on 256 CUs; chunked, the wiki shape (200 x 9,227) is 13 x 37 workgroups.  Partials cost n_src · chunks · k · 8 B.
 // No atomics, no allocation, no host synchronisation: graph-capturable, run-to-run identical.
 //
-// Two more entry points share Hs / Hd, the fma chain, the order and topk_merge:
-//   tgnx_link_predictor_topk_filtered   per-source exclusions by key: topk_pairs<true> writes NaN over an excluded
-//                                       pair's LDS entry after out_all got the logit;
-//   tgnx_link_predictor_topk_lists      a candidate list per source: topk_list_pairs, one workgroup per (source,
-//                                       chunk of the list), positions = slots in the list; topk_list_idx.
+// Three more entry points score the same pairs.  What they have in common is written once, and every kernel below
+// is described by what is its own:
+//   project_rows                   (host) the Hs / Hd GEMMs into the workspace carve_ws lays out;
+//   stage_tile                     a tile's Hs rows (k-major) and w_out into LDS, zero past D and past n_src;
+//   pair_chain<NQ>                 THE fma chain: a candidate's Hd row against NQ staged Hs rows (16: the tile; 1: one
+//                                  source).  Every logit any kernel here produces has the bits this function gives;
+//   stage_filter, excluded_mask    a tile's exclusion segments, clamped into the arrays, and a candidate's mask;
+//   select_chunk<QW>               k rounds of pick-after-previous over logits in LDS, the partial list written;
+//   topk_merge (launch_merge)      the partial lists' k best.
+//
+//   tgnx_link_predictor_topk_filtered  per-source exclusions by key: topk_pairs<true> writes NaN over
+//                  an excluded pair's LDS entry after out_all got the logit;
+//   tgnx_link_predictor_topk_lists     a candidate list per source: topk_list_pairs, one workgroup per
+//                  (source, chunk of the list), positions = slots in the list; topk_list_idx.
 //
 // tgnx_link_predictor_rank wants less than a selection: where each source's true destination stands
-// among the candidates, i.e. per source three counts (logits above the target's, equal to it, compared at all).  Same
-// Hs / Hd GEMMs, same chain, same exclusion staging; no LDS logit matrix, no select rounds, no merge:
-//   rank_target  a wave per source: tl[q] = logit(q, target[q]) by the chain over the padded row (as
-//                topk_list_pairs does for a list entry; NaN at a target outside z_cand), and the three counters zeroed;
+// among the candidates, i.e. per source three counts (logits above the target's, equal to it, compared at all).  No
+// LDS logit matrix, no select rounds, no merge:
+//   rank_target  a wave per source: tl[q] = logit(q, target[q]) in pair_chain's order (NaN at a target outside
+//                z_cand), and the three counters zeroed;
 //   rank_pairs   one workgroup per (tile of 16 sources, chunk of 256 candidates), a thread per candidate: its 16
 //                logits against the tile's 16 tl in LDS, the key rules, then per source a ballot and a population
 //                count per counter (scalar instructions: exact, and cheaper than three DPP sums), the four waves'
@@ -76,15 +85,20 @@ int chunk_of(int64_t n_src, int64_t n_cand) {
 }
 size_t pairs_smem(int64_t ldh, int chunk) { return (size_t)(ldh * TK_TQ + ldh + (int64_t)TK_TQ * chunk) * sizeof(float); }
 
+// partial lists per source.  Dense: sized for the smaller chunk (the larger count), so the size is monotone in n_cand
+int64_t dense_lists(int64_t n_cand) { return ceil_div(n_cand, TK_CHUNK_MIN); }
+int64_t list_chunks(int64_t max_len) { return std::max<int64_t>(1, ceil_div(max_len, TK_LCHUNK)); }
+
+// The workspace of every entry point: Hs, Hd, `lists` partial lists of k (value, position) per source (rank: none),
+// then the GEMM scratch from `used` on.
 struct TopkWs {
   float *hs, *hd, *pval;
   int* pidx;
   char* gemm;
   size_t used;
 };
-// the partial lists are sized for the smaller chunk (the larger count), so the size is monotone in n_cand
-TopkWs topk_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D, int32_t k) {
-  const int64_t ldh = ld_of(D), ncmax = ceil_div(n_cand, TK_CHUNK_MIN);
+TopkWs carve_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D, int32_t k, int64_t lists) {
+  const int64_t ldh = ld_of(D);
   char* p = reinterpret_cast<char*>(ws);
   size_t off = 0;
   TopkWs w;
@@ -93,13 +107,21 @@ TopkWs topk_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D, int32_t k) {
   w.hd = reinterpret_cast<float*>(p + off);
   off += align256((size_t)n_cand * ldh * 4);
   w.pval = reinterpret_cast<float*>(p + off);
-  off += align256((size_t)n_src * ncmax * k * 4);
+  off += align256((size_t)n_src * lists * k * 4);
   w.pidx = reinterpret_cast<int*>(p + off);
-  off += align256((size_t)n_src * ncmax * k * 4);
+  off += align256((size_t)n_src * lists * k * 4);
   w.gemm = p + off;
   w.used = off;
   return w;
 }
+// what the *_ws_bytes functions return for valid sizes
+size_t ws_bytes_of(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k, int64_t lists) {
+  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
+                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
+  return carve_ws(nullptr, n_src, n_cand, D, k, lists).used + align256(g) + 256;
+}
+
+constexpr float TK_QNAN = __builtin_bit_cast(float, 0x7fc00000);  // the quiet NaN of skipped and excluded entries
 
 // the pick after (pv, pj) in the order among a lane's entries (v, j): larger v, then smaller j
 __device__ __forceinline__ bool after(float v, int j, float pv, int pj) { return v < pv || (v == pv && j > pj); }
@@ -116,7 +138,7 @@ struct TopkFilter {
   const int64_t *cand_key, *src_key, *excl_ptr, *excl_key;
   int64_t nnz;
 };
-// LDS beside the logits (filtered kernel): the tile's exclusion segments when they fit, their bounds, the source keys
+// LDS of the filtered kernels (stage_filter): the tile's exclusion segments when they fit, their bounds, the source keys
 struct TopkFilterLds {
   int64_t key[TK_EXCAP];
   int64_t lo[TK_TQ], hi[TK_TQ], skey[TK_TQ];
@@ -141,92 +163,99 @@ __device__ __forceinline__ bool seg_has(const int64_t* a, Int lo, Int hi, int64_
   return lo < hi && a[lo] == key;
 }
 
-template <bool FILT>
-__global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_cand, int D, int ldh, int chunk, int nc,
-                                                       const float* __restrict__ hs, const float* __restrict__ hd,
-                                                       const float* __restrict__ w_out, const float* __restrict__ b_out,
-                                                       int k, float* __restrict__ pval, int* __restrict__ pidx,
-                                                       float* __restrict__ out_all, TopkFilter f) {
-  extern __shared__ __attribute__((aligned(16))) float tk_smem[];
-  float* hsT = tk_smem;                     // [ldh][16] the tile's Hs rows, k-major; rows past n_src and columns past D zero
-  float* wl = hsT + (size_t)ldh * TK_TQ;    // [ldh] w_out, zero past D
-  float* L = wl + ldh;                      // [16][chunk] the chunk's logits
-  const int tid = threadIdx.x;
-  const int64_t tile = blockIdx.x / nc, q0 = tile * TK_TQ;
-  const int64_t cbase = (int64_t)(blockIdx.x % nc) * chunk;
-  const int nq = (int)min((int64_t)TK_TQ, n_src - q0);
-  const int nvalid = (int)min((int64_t)chunk, n_cand - cbase);
-  // (ldh and chunk are multiples of 4: the struct starts 16-B aligned)
-  TopkFilterLds* X = reinterpret_cast<TopkFilterLds*>(L + (size_t)TK_TQ * chunk);
-  if constexpr (FILT) {
-    // the tile's segments, their pointers clamped into [0, nnz] and a decreasing pair read as empty; staged in LDS
-    // when the tile's keys fit (ring rows: 16 x <= 32), searched in global memory otherwise
-    if (tid < TK_TQ) {
-      int64_t lo = 0, hi = 0;
-      if (f.excl_ptr && tid < nq) {
-        lo = clamp64(f.excl_ptr[q0 + tid], 0, f.nnz);
-        hi = max(lo, clamp64(f.excl_ptr[q0 + tid + 1], 0, f.nnz));
-      }
-      X->lo[tid] = lo;
-      X->hi[tid] = hi;
-      X->has_skey[tid] = f.src_key && tid < nq;
-      X->skey[tid] = (f.src_key && tid < nq) ? f.src_key[q0 + tid] : 0;
+// The tile's segments, their pointers clamped into [0, nnz] and a decreasing pair read as empty: whatever excl_ptr
+// holds, no read leaves excl_key.  Staged in LDS when the tile's keys fit (ring rows: 16 x <= 32), searched in global
+// memory otherwise.  (Two barriers inside; the caller's barrier after stage_tile publishes the keys.)
+__device__ __forceinline__ void stage_filter(TopkFilterLds* X, const TopkFilter& f, int64_t q0, int nq, int tid) {
+  if (tid < TK_TQ) {
+    int64_t lo = 0, hi = 0;
+    if (f.excl_ptr && tid < nq) {
+      lo = clamp64(f.excl_ptr[q0 + tid], 0, f.nnz);
+      hi = max(lo, clamp64(f.excl_ptr[q0 + tid + 1], 0, f.nnz));
     }
-    __syncthreads();
-    if (tid == 0) {
-      int64_t tot = 0;
-      for (int i = 0; i < TK_TQ; ++i) {
-        X->off[i] = (int)min(tot, (int64_t)TK_EXCAP);
-        tot += X->hi[i] - X->lo[i];
-      }
-      X->staged = tot <= TK_EXCAP;
-    }
-    __syncthreads();
-    if (X->staged)
-      for (int i = 0; i < TK_TQ; ++i) {
-        const int64_t lo = X->lo[i];
-        const int len = (int)(X->hi[i] - lo), off = X->off[i];
-        for (int x = tid; x < len; x += TK_BLOCK) X->key[off + x] = f.excl_key[lo + x];
-      }
+    X->lo[tid] = lo;
+    X->hi[tid] = hi;
+    X->has_skey[tid] = f.src_key && tid < nq;
+    X->skey[tid] = (f.src_key && tid < nq) ? f.src_key[q0 + tid] : 0;
   }
+  __syncthreads();
+  if (tid == 0) {
+    int64_t tot = 0;
+    for (int i = 0; i < TK_TQ; ++i) {
+      X->off[i] = (int)min(tot, (int64_t)TK_EXCAP);
+      tot += X->hi[i] - X->lo[i];
+    }
+    X->staged = tot <= TK_EXCAP;
+  }
+  __syncthreads();
+  if (X->staged)
+    for (int i = 0; i < TK_TQ; ++i) {
+      const int64_t lo = X->lo[i];
+      const int len = (int)(X->hi[i] - lo), off = X->off[i];
+      for (int x = tid; x < len; x += TK_BLOCK) X->key[off + x] = f.excl_key[lo + x];
+    }
+}
+// bit i: the candidate with key ck is out for the tile's source i
+__device__ __forceinline__ unsigned excluded_mask(const TopkFilterLds* X, const TopkFilter& f, int nq, int64_t ck) {
+  unsigned excl = 0;
+  const bool staged = X->staged;
+  for (int i = 0; i < nq; ++i) {
+    bool out = X->has_skey[i] && X->skey[i] == ck;
+    const int64_t lo = X->lo[i], hi = X->hi[i];
+    if (!out && hi > lo)
+      out = staged ? seg_has<int>(X->key, X->off[i], X->off[i] + (int)(hi - lo), ck)
+                   : seg_has<int64_t>(f.excl_key, lo, hi, ck);
+    excl |= (unsigned)out << i;
+  }
+  return excl;
+}
+
+// hsT [ldh][16]: the Hs rows of sources q0 .. q0 + 15, k-major; rows past nq and columns past D zero.  wl [ldh]:
+// w_out, zero past D.
+__device__ __forceinline__ void stage_tile(float* hsT, float* wl, const float* __restrict__ hs,
+                                           const float* __restrict__ w_out, int64_t q0, int nq, int D, int ldh,
+                                           int tid) {
   for (int x = tid; x < ldh * TK_TQ; x += TK_BLOCK) {
     const int kk = x / TK_TQ, q = x % TK_TQ;
     hsT[x] = (q < nq && kk < D) ? hs[(q0 + q) * ldh + kk] : 0.f;
   }
   for (int x = tid; x < ldh; x += TK_BLOCK) wl[x] = x < D ? w_out[x] : 0.f;
-  __syncthreads();
-  const float bo = b_out[0];
-  for (int c0 = 0; c0 < chunk; c0 += TK_BLOCK) {  // (block-uniform)
-    const int cl = c0 + tid;
-    const bool valid = cl < nvalid;
-    // a thread past the chunk's end reads the last valid row (in bounds, result discarded)
-    const float4* row = reinterpret_cast<const float4*>(hd + (cbase + min(cl, nvalid - 1)) * ldh);
-    float acc[TK_TQ];
+}
+
+// The chain that fixes a logit's bits: acc[q] = fma(w_k, relu(Hs[q][k] + Hd[c][k]), acc[q]) for k ascending over the
+// padded row (nv 16-B vectors), the pad columns (k >= D, which the GEMM does not write) read as zero.  `row` is the
+// candidate's Hd row, wl the staged w_out (zero past D), hs the staged Hs: stage_tile's [ldh][16] tile for
+// NQ = TK_TQ, one row [ldh] (zero past D) for NQ = 1.  Every kernel's logits come from here (rank_target restates
+// the order), which is what makes the dense, list and rank logits of a pair equal bit for bit.
+// The row comes in groups of TK_G vectors, the next group's loads in flight while this one is used (a load per
+// iteration and its use right behind it left the L2 latency exposed 25 times per row at D = 100).  Past the row's
+// end the last vector is loaded again and not used.
+template <int NQ>
+__device__ __forceinline__ void pair_chain(const float4* __restrict__ row, int nv, int D, const float* __restrict__ wl,
+                                           const float* __restrict__ hs, float (&acc)[NQ]) {
+  static_assert(NQ == 1 || NQ == TK_TQ, "one source or a tile");
+  float4 nxt[TK_G];
 #pragma unroll
-    for (int i = 0; i < TK_TQ; ++i) acc[i] = 0.f;
-    // the row in groups of TK_G 16-B vectors, the next group's loads in flight while this one is used (a load per
-    // iteration and its use right behind it left the L2 latency exposed 25 times per row at D = 100).  Past the
-    // row's end the last vector is loaded again and not used.
-    const int nv = ldh >> 2;
-    float4 nxt[TK_G];
+  for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
+  for (int v0 = 0; v0 < nv; v0 += TK_G) {
+    float4 cur[TK_G];
 #pragma unroll
-    for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
-    for (int v0 = 0; v0 < nv; v0 += TK_G) {
-      float4 cur[TK_G];
+    for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
 #pragma unroll
-      for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
+    for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
 #pragma unroll
-      for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
+    for (int u = 0; u < TK_G; ++u) {
+      if (v0 + u >= nv) break;  // (uniform)
+      const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
 #pragma unroll
-      for (int u = 0; u < TK_G; ++u) {
-        if (v0 + u >= nv) break;  // (uniform)
-        const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int kk = (v0 + u) * 4 + e;
-          const float hv = kk < D ? he[e] : 0.f;  // (the row's pad columns are not written by the GEMM)
-          const float wk = wl[kk];
-          const float4* hq = reinterpret_cast<const float4*>(hsT + kk * TK_TQ);
+      for (int e = 0; e < 4; ++e) {
+        const int kk = (v0 + u) * 4 + e;
+        const float hv = kk < D ? he[e] : 0.f;
+        const float wk = wl[kk];
+        if constexpr (NQ == 1) {
+          acc[0] = fmaf(wk, fmaxf(hs[kk] + hv, 0.f), acc[0]);
+        } else {
+          const float4* hq = reinterpret_cast<const float4*>(hs + kk * TK_TQ);
 #pragma unroll
           for (int g = 0; g < TK_TQ / 4; ++g) {
             const float4 s = hq[g];
@@ -238,35 +267,16 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_
         }
       }
     }
-    // an excluded pair's entry in LDS becomes NaN, which the select never picks; out_all keeps the logit
-    unsigned excl = 0;
-    if constexpr (FILT) {
-      const int64_t cpos = cbase + min(cl, nvalid - 1);
-      const int64_t ck = f.cand_key ? f.cand_key[cpos] : cpos;
-      const bool staged = X->staged;
-      for (int i = 0; i < nq; ++i) {
-        bool out = X->has_skey[i] && X->skey[i] == ck;
-        const int64_t lo = X->lo[i], hi = X->hi[i];
-        if (!out && hi > lo)
-          out = staged ? seg_has<int>(X->key, X->off[i], X->off[i] + (int)(hi - lo), ck)
-                       : seg_has<int64_t>(f.excl_key, lo, hi, ck);
-        excl |= (unsigned)out << i;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < TK_TQ; ++i) {
-      const float lg = acc[i] + bo;
-      // (entries past nvalid are never scanned)
-      L[i * chunk + cl] = (FILT && ((excl >> i) & 1u)) ? __int_as_float(0x7fc00000) : lg;
-      if (out_all && valid && i < nq) out_all[(q0 + i) * n_cand + cbase + cl] = lg;
-    }
   }
-  __syncthreads();
-  // the chunk's k best per source: wave w takes sources 4 w .. 4 w + 3, their four selections side by side (four
-  // independent scan / reduce chains per round; rows past nq hold the zero source's logits and are not stored)
-  constexpr int QW = TK_TQ / (TK_BLOCK / WAVE);
-  const int lane = tid & 63, i0 = (tid >> 6) * QW;
-  const int64_t cj = blockIdx.x % nc;
+}
+
+// A wave's k rounds of pick-after-previous over QW rows of logits in LDS (row u at L + u * stride, entries
+// [0, nvalid)), side by side: QW independent scan / reduce chains per round.  Row u < nrows is source row0 + u, whose
+// partial list for chunk cj gets the picks in order, positions offset by pos0; none left: (-inf, -1), the padding.
+template <int QW>
+__device__ __forceinline__ void select_chunk(const float* L, int stride, int nvalid, int k, int lane, int64_t row0,
+                                             int nrows, int nc, int64_t cj, int pos0, float* __restrict__ pval,
+                                             int* __restrict__ pidx) {
   float pv[QW];
   int pj[QW];
 #pragma unroll
@@ -285,7 +295,7 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_
     for (int j = lane; j < nvalid; j += WAVE) {  // j ascends: the first of a lane's equal values stays
 #pragma unroll
       for (int u = 0; u < QW; ++u) {
-        const float v = L[(i0 + u) * chunk + j];
+        const float v = L[u * stride + j];
         if (after(v, j, pv[u], pj[u]) && (v > bv[u] || bj[u] == INT_MAX)) {
           bv[u] = v;
           bj[u] = j;
@@ -295,14 +305,62 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_
 #pragma unroll
     for (int u = 0; u < QW; ++u) {
       wave_best(bv[u], bj[u]);
-      if (lane == 0 && i0 + u < nq) {  // (none left, position INT_MAX: padding)
-        pval[((q0 + i0 + u) * nc + cj) * k + r] = bj[u] == INT_MAX ? -INFINITY : L[(i0 + u) * chunk + bj[u]];
-        pidx[((q0 + i0 + u) * nc + cj) * k + r] = bj[u] == INT_MAX ? -1 : (int)(cbase + bj[u]);
+      if (lane == 0 && u < nrows) {
+        pval[((row0 + u) * nc + cj) * k + r] = bj[u] == INT_MAX ? -INFINITY : L[u * stride + bj[u]];
+        pidx[((row0 + u) * nc + cj) * k + r] = bj[u] == INT_MAX ? -1 : pos0 + bj[u];
       }
       pv[u] = bv[u];
       pj[u] = bj[u];
     }
   }
+}
+
+template <bool FILT>
+__global__ void __launch_bounds__(TK_BLOCK) topk_pairs(int64_t n_src, int64_t n_cand, int D, int ldh, int chunk, int nc,
+                                                       const float* __restrict__ hs, const float* __restrict__ hd,
+                                                       const float* __restrict__ w_out, const float* __restrict__ b_out,
+                                                       int k, float* __restrict__ pval, int* __restrict__ pidx,
+                                                       float* __restrict__ out_all, TopkFilter f) {
+  extern __shared__ __attribute__((aligned(16))) float tk_smem[];
+  float* hsT = tk_smem;                     // [ldh][16] (stage_tile)
+  float* wl = hsT + (size_t)ldh * TK_TQ;    // [ldh]
+  float* L = wl + ldh;                      // [16][chunk] the chunk's logits
+  const int tid = threadIdx.x;
+  const int64_t tile = blockIdx.x / nc, q0 = tile * TK_TQ;
+  const int64_t cj = blockIdx.x % nc, cbase = cj * chunk;
+  const int nq = (int)min((int64_t)TK_TQ, n_src - q0);
+  const int nvalid = (int)min((int64_t)chunk, n_cand - cbase);
+  // (ldh and chunk are multiples of 4: the struct starts 16-B aligned)
+  TopkFilterLds* X = reinterpret_cast<TopkFilterLds*>(L + (size_t)TK_TQ * chunk);
+  if constexpr (FILT) stage_filter(X, f, q0, nq, tid);
+  stage_tile(hsT, wl, hs, w_out, q0, nq, D, ldh, tid);
+  __syncthreads();
+  const float bo = b_out[0];
+  for (int c0 = 0; c0 < chunk; c0 += TK_BLOCK) {  // (block-uniform)
+    const int cl = c0 + tid;
+    const bool valid = cl < nvalid;
+    // a thread past the chunk's end reads the last valid row (in bounds, result discarded)
+    const int64_t cpos = cbase + min(cl, nvalid - 1);
+    float acc[TK_TQ];
+#pragma unroll
+    for (int i = 0; i < TK_TQ; ++i) acc[i] = 0.f;
+    pair_chain<TK_TQ>(reinterpret_cast<const float4*>(hd + cpos * ldh), ldh >> 2, D, wl, hsT, acc);
+    // an excluded pair's entry in LDS becomes NaN, which the select never picks; out_all keeps the logit
+    unsigned excl = 0;
+    if constexpr (FILT) excl = excluded_mask(X, f, nq, f.cand_key ? f.cand_key[cpos] : cpos);
+#pragma unroll
+    for (int i = 0; i < TK_TQ; ++i) {
+      const float lg = acc[i] + bo;
+      // (entries past nvalid are never scanned)
+      L[i * chunk + cl] = (FILT && ((excl >> i) & 1u)) ? TK_QNAN : lg;
+      if (out_all && valid && i < nq) out_all[(q0 + i) * n_cand + cbase + cl] = lg;
+    }
+  }
+  __syncthreads();
+  // wave w takes sources 4 w .. 4 w + 3 (rows past nq hold the zero source's logits and are not stored)
+  constexpr int QW = TK_TQ / (TK_BLOCK / WAVE);
+  const int i0 = (tid >> 6) * QW;
+  select_chunk<QW>(L + i0 * chunk, chunk, nvalid, k, tid & 63, q0 + i0, nq - i0, nc, cj, (int)cbase, pval, pidx);
 }
 
 // Wave per source: the k best of its nc chunk lists (k entries each, sorted in the order, position -1: the padding
@@ -400,9 +458,8 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_merge(int64_t n_src, int nc, in
 }
 
 // Per-source candidate lists (tgnx_link_predictor_topk_lists): one workgroup per (source, chunk of TK_LCHUNK list
-// entries).  Hs[q] and w_out sit in LDS; a thread owns one entry and streams its gathered Hd row 16 B at a time through
-// the same fma chain as topk_pairs (k ascending over the padded row, the pad columns zero), so the logit of (q, c) has
-// the bits of the dense operator's.  Wave 0 then picks the chunk's k best by the same pick-after-previous selection,
+// entries).  Hs[q] and w_out sit in LDS; a thread owns one entry and runs its gathered Hd row through pair_chain<1>,
+// so the logit of (q, c) has the bits of the dense operator's.  Wave 0 then picks the chunk's k best (select_chunk<1>),
 // positions being slots in the source's list.  Skipped entries (negative, >= n_cand, slot >= max_len) hold NaN.  The
 // list's bounds are clamped into [0, nnz]; slots past the grid's reach (>= nc * TK_LCHUNK) are swept by the last chunk.
 __global__ void __launch_bounds__(TK_LCHUNK) topk_list_pairs(int64_t n_cand, int D, int ldh, int nc, int64_t nnz,
@@ -429,47 +486,24 @@ __global__ void __launch_bounds__(TK_LCHUNK) topk_list_pairs(int64_t n_cand, int
     wl[x] = x < D ? w_out[x] : 0.f;
   }
   __syncthreads();
-  const float qnan = __int_as_float(0x7fc00000);
   const int64_t s = (int64_t)cj * TK_LCHUNK + tid;
   int bad = 0;
-  float lg = qnan;
+  float lg = TK_QNAN;
   if (s < len) {
     const int64_t c = list_idx[lo + s];
     const bool within = s < max_len;
     bad = !within || c >= n_cand;
     if (within && c >= 0 && c < n_cand) {
-      const float4* row = reinterpret_cast<const float4*>(hd + c * ldh);
-      const int nv = ldh >> 2;
-      float acc = 0.f;
-      float4 nxt[TK_G];
-#pragma unroll
-      for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
-      for (int v0 = 0; v0 < nv; v0 += TK_G) {
-        float4 cur[TK_G];
-#pragma unroll
-        for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
-#pragma unroll
-        for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
-#pragma unroll
-        for (int u = 0; u < TK_G; ++u) {
-          if (v0 + u >= nv) break;
-          const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int kk = (v0 + u) * 4 + e;
-            const float hv = kk < D ? he[e] : 0.f;
-            acc = fmaf(wl[kk], fmaxf(hq[kk] + hv, 0.f), acc);
-          }
-        }
-      }
-      lg = acc + b_out[0];
+      float acc[1] = {0.f};
+      pair_chain<1>(reinterpret_cast<const float4*>(hd + c * ldh), ldh >> 2, D, wl, hq, acc);
+      lg = acc[0] + b_out[0];
     }
     if (out_logits) out_logits[lo + s] = lg;
   }
   L[tid] = lg;
   if (cj == nc - 1)
     for (int64_t t = (int64_t)nc * TK_LCHUNK + tid; t < len; t += TK_LCHUNK) {
-      if (out_logits) out_logits[lo + t] = qnan;
+      if (out_logits) out_logits[lo + t] = TK_QNAN;
       bad += 1;
     }
   if (n_invalid) {  // (block-uniform) the one atomic: an integer count
@@ -486,26 +520,7 @@ __global__ void __launch_bounds__(TK_LCHUNK) topk_list_pairs(int64_t n_cand, int
     if (b) atomicAdd(n_invalid, (unsigned long long)b);
   }
   const int nvalid = (int)max((int64_t)0, min((int64_t)TK_LCHUNK, len - (int64_t)cj * TK_LCHUNK));
-  float pv = INFINITY;
-  int pj = -1;
-  for (int r = 0; r < k; ++r) {
-    float bv = -INFINITY;
-    int bj = INT_MAX;
-    for (int j = lane; j < nvalid; j += WAVE) {
-      const float v = L[j];
-      if (after(v, j, pv, pj) && (v > bv || bj == INT_MAX)) {
-        bv = v;
-        bj = j;
-      }
-    }
-    wave_best(bv, bj);
-    if (lane == 0) {
-      pval[(q * nc + cj) * k + r] = bj == INT_MAX ? -INFINITY : L[bj];
-      pidx[(q * nc + cj) * k + r] = bj == INT_MAX ? -1 : cj * TK_LCHUNK + bj;
-    }
-    pv = bv;
-    pj = bj;
-  }
+  select_chunk<1>(L, 0, nvalid, k, lane, q, 1, nc, cj, cj * TK_LCHUNK, pval, pidx);
 }
 
 // out_idx[q][r] = the candidate position at the selected slot of q's list (-1 at the padding)
@@ -522,11 +537,12 @@ __global__ void __launch_bounds__(TK_BLOCK) topk_list_idx(int64_t n_src, int k, 
 }
 
 // ---------------------------------------------------------------- rank of a given target (tgnx_link_predictor_rank)
-// tl[q] = logit(q, target[q]): topk_list_pairs' per-entry chain (k ascending over the padded row, the pad columns
-// zero), so the bits of the dense operator's out_all[q][target[q]]; NaN at a target outside [0, n_cand).  A wave per
-// source: the lanes load the two rows once, coalesced, and leave w_k and relu(Hs[q][k] + Hd[p][k]) in LDS; lane 0
-// then runs the chain's fmas in order.  (A thread per source walking both rows took 9.7 us at 200 x 9,227 x 100:
-// seven dependent rounds of loads.)  The three counters start at zero here, before rank_pairs adds to them.
+// tl[q] = logit(q, target[q]) with the bits of the dense operator's out_all[q][target[q]]; NaN at a target outside
+// [0, n_cand).  It does not call pair_chain but has to reproduce its order: the same terms, fma'd for k ascending
+// over the padded row with the pad columns zero.  A wave per source: the lanes load the two rows once, coalesced, and
+// leave w_k and relu(Hs[q][k] + Hd[p][k]) in LDS; lane 0 then runs the chain's fmas in order.  (A thread per source
+// walking both rows, pair_chain<1>'s form, took 9.7 us at 200 x 9,227 x 100: seven dependent rounds of loads.)  The
+// three counters start at zero here, before rank_pairs adds to them.
 __global__ void __launch_bounds__(TK_BLOCK) rank_target(int64_t n_src, int64_t n_cand, int D, int ldh,
                                                         const int64_t* __restrict__ target,
                                                         const float* __restrict__ hs, const float* __restrict__ hd,
@@ -550,7 +566,7 @@ __global__ void __launch_bounds__(TK_BLOCK) rank_target(int64_t n_src, int64_t n
     }
   __syncthreads();
   if (!live || lane != 0) return;
-  float lg = __int_as_float(0x7fc00000);
+  float lg = TK_QNAN;
   if (inside) {
     float acc = 0.f;
     for (int kk = 0; kk < ldh; ++kk) acc = fmaf(sw[wv][kk], st[wv][kk], acc);
@@ -570,10 +586,10 @@ struct RankLds {
   int cnt[TK_BLOCK / WAVE][3 * TK_TQ];
 };
 
-// One workgroup per (tile of 16 sources, chunk of TK_BLOCK competing candidates), a thread per candidate; the pair
-// loop is topk_pairs'.  Candidate c counts for source i when its logit is not NaN, its key is not the target's (which
-// covers c == target), not the source's and not in the source's segment.  With tl NaN (a skipped row) neither
-// comparison holds: gt = eq = 0 and n is still the size of the compared set.
+// One workgroup per (tile of 16 sources, chunk of TK_BLOCK competing candidates), a thread per candidate and its 16
+// logits from pair_chain.  Candidate c counts for source i when its logit is not NaN, its key is not the target's
+// (which covers c == target), not the source's and not in the source's segment.  With tl NaN (a skipped row)
+// neither comparison holds: gt = eq = 0 and n is still the size of the compared set.
 template <bool FILT>
 __global__ void __launch_bounds__(TK_BLOCK) rank_pairs(int64_t n_src, int64_t n_cand, int64_t n_count, int D, int ldh,
                                                        int nc, const float* __restrict__ hs,
@@ -585,7 +601,7 @@ __global__ void __launch_bounds__(TK_BLOCK) rank_pairs(int64_t n_src, int64_t n_
                                                        unsigned long long* __restrict__ eq,
                                                        unsigned long long* __restrict__ n) {
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];
-  float* hsT = rk_smem;                    // [ldh][16] as in topk_pairs
+  float* hsT = rk_smem;                    // [ldh][16] (stage_tile)
   float* wl = hsT + (size_t)ldh * TK_TQ;   // [ldh]
   RankLds* R = reinterpret_cast<RankLds*>(wl + ldh);  // (17 ldh floats: 16-B aligned)
   TopkFilterLds* X = reinterpret_cast<TopkFilterLds*>(R + 1);
@@ -599,96 +615,22 @@ __global__ void __launch_bounds__(TK_BLOCK) rank_pairs(int64_t n_src, int64_t n_
     const bool in = p >= 0 && p < n_cand;
     R->thas[tid] = in;
     R->tkey[tid] = in ? (f.cand_key ? f.cand_key[p] : p) : 0;
-    R->tl[tid] = tid < nq ? tlogit[q0 + tid] : __int_as_float(0x7fc00000);
+    R->tl[tid] = tid < nq ? tlogit[q0 + tid] : TK_QNAN;
   }
-  if constexpr (FILT) {
-    // topk_pairs<true>'s staging: pointers clamped into [0, nnz], a decreasing pair empty, LDS when the keys fit
-    if (tid < TK_TQ) {
-      int64_t lo = 0, hi = 0;
-      if (f.excl_ptr && tid < nq) {
-        lo = clamp64(f.excl_ptr[q0 + tid], 0, f.nnz);
-        hi = max(lo, clamp64(f.excl_ptr[q0 + tid + 1], 0, f.nnz));
-      }
-      X->lo[tid] = lo;
-      X->hi[tid] = hi;
-      X->has_skey[tid] = f.src_key && tid < nq;
-      X->skey[tid] = (f.src_key && tid < nq) ? f.src_key[q0 + tid] : 0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int64_t tot = 0;
-      for (int i = 0; i < TK_TQ; ++i) {
-        X->off[i] = (int)min(tot, (int64_t)TK_EXCAP);
-        tot += X->hi[i] - X->lo[i];
-      }
-      X->staged = tot <= TK_EXCAP;
-    }
-    __syncthreads();
-    if (X->staged)
-      for (int i = 0; i < TK_TQ; ++i) {
-        const int64_t lo = X->lo[i];
-        const int len = (int)(X->hi[i] - lo), off = X->off[i];
-        for (int x = tid; x < len; x += TK_BLOCK) X->key[off + x] = f.excl_key[lo + x];
-      }
-  }
-  for (int x = tid; x < ldh * TK_TQ; x += TK_BLOCK) {
-    const int kk = x / TK_TQ, q = x % TK_TQ;
-    hsT[x] = (q < nq && kk < D) ? hs[(q0 + q) * ldh + kk] : 0.f;
-  }
-  for (int x = tid; x < ldh; x += TK_BLOCK) wl[x] = x < D ? w_out[x] : 0.f;
+  if constexpr (FILT) stage_filter(X, f, q0, nq, tid);
+  stage_tile(hsT, wl, hs, w_out, q0, nq, D, ldh, tid);
   __syncthreads();
   const float bo = b_out[0];
   const bool valid = tid < nvalid;
   // a thread past the chunk's end reads the last valid row (in bounds, counted nowhere)
   const int64_t cpos = cbase + min(tid, nvalid - 1);
-  const float4* row = reinterpret_cast<const float4*>(hd + cpos * ldh);
   float acc[TK_TQ];
 #pragma unroll
   for (int i = 0; i < TK_TQ; ++i) acc[i] = 0.f;
-  const int nv = ldh >> 2;
-  float4 nxt[TK_G];
-#pragma unroll
-  for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(u, nv - 1)];
-  for (int v0 = 0; v0 < nv; v0 += TK_G) {
-    float4 cur[TK_G];
-#pragma unroll
-    for (int u = 0; u < TK_G; ++u) cur[u] = nxt[u];
-#pragma unroll
-    for (int u = 0; u < TK_G; ++u) nxt[u] = row[min(v0 + TK_G + u, nv - 1)];
-#pragma unroll
-    for (int u = 0; u < TK_G; ++u) {
-      if (v0 + u >= nv) break;  // (uniform)
-      const float he[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int kk = (v0 + u) * 4 + e;
-        const float hv = kk < D ? he[e] : 0.f;
-        const float wk = wl[kk];
-        const float4* hq = reinterpret_cast<const float4*>(hsT + kk * TK_TQ);
-#pragma unroll
-        for (int g = 0; g < TK_TQ / 4; ++g) {
-          const float4 s = hq[g];
-          acc[4 * g + 0] = fmaf(wk, fmaxf(s.x + hv, 0.f), acc[4 * g + 0]);
-          acc[4 * g + 1] = fmaf(wk, fmaxf(s.y + hv, 0.f), acc[4 * g + 1]);
-          acc[4 * g + 2] = fmaf(wk, fmaxf(s.z + hv, 0.f), acc[4 * g + 2]);
-          acc[4 * g + 3] = fmaf(wk, fmaxf(s.w + hv, 0.f), acc[4 * g + 3]);
-        }
-      }
-    }
-  }
+  pair_chain<TK_TQ>(reinterpret_cast<const float4*>(hd + cpos * ldh), ldh >> 2, D, wl, hsT, acc);
   const int64_t ck = f.cand_key ? f.cand_key[cpos] : cpos;
   unsigned excl = 0;
-  if constexpr (FILT) {
-    const bool staged = X->staged;
-    for (int i = 0; i < nq; ++i) {
-      bool out = X->has_skey[i] && X->skey[i] == ck;
-      const int64_t lo = X->lo[i], hi = X->hi[i];
-      if (!out && hi > lo)
-        out = staged ? seg_has<int>(X->key, X->off[i], X->off[i] + (int)(hi - lo), ck)
-                     : seg_has<int64_t>(f.excl_key, lo, hi, ck);
-      excl |= (unsigned)out << i;
-    }
-  }
+  if constexpr (FILT) excl = excluded_mask(X, f, nq, ck);
   const int lane = tid & 63, wv = tid >> 6;
 #pragma unroll
   for (int i = 0; i < TK_TQ; ++i) {
@@ -715,49 +657,41 @@ size_t rank_smem(int64_t ldh, bool filt) {
   return (size_t)(ldh * TK_TQ + ldh) * sizeof(float) + sizeof(RankLds) + (filt ? sizeof(TopkFilterLds) : 0);
 }
 
-struct RankWs {
-  float *hs, *hd;
-  char* gemm;
-  size_t used;
-};
-RankWs rank_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D) {
-  const int64_t ldh = ld_of(D);
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
-  RankWs w;
-  w.hs = reinterpret_cast<float*>(p + off);
-  off += align256((size_t)n_src * ldh * 4);
-  w.hd = reinterpret_cast<float*>(p + off);
-  off += align256((size_t)n_cand * ldh * 4);
-  w.gemm = p + off;
-  w.used = off;
-  return w;
+// The checks the three entry points share, in one wording: k (rank passes 1), the sizes with n_cand < n_cand_end (so
+// that a position plus the entry point's chunk stays inside an int), and the pointers all of them take; `own` says
+// that the entry point's own pointers are there.
+int check_common(const char* name, int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k,
+                 int64_t n_cand_end, const void* z_cand, const void* w_src, const void* w_dst, const void* w_out,
+                 const void* b_out, const void* ws, bool own) {
+  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "%s: k must be in [1, %d], got %d", name, TGNX_TOPK_MAX, k);
+  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
+                     n_cand < n_cand_end && n_src < (int64_t(1) << 31),
+                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
+  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && own && (n_cand == 0 || z_cand), "%s: null pointer", name);
+  return TGNX_OK;
 }
 
-struct ListWs {
-  float *hs, *hd, *pval;
-  int* pidx;
-  char* gemm;
-  size_t used;
-  int64_t nc;
-};
-ListWs list_ws(void* ws, int64_t n_src, int64_t n_cand, int64_t D, int32_t k, int64_t max_len) {
+// Hs = z_src W_src^T + b_src and Hd = z_cand W_dst^T + b_dst into the workspace, the same two GEMMs for every entry
+// point.  (n_cand = 0: neither is computed, neither is used.)
+int project_rows(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src, const float* z_cand,
+                 const float* w_src, const float* b_src, const float* w_dst, const float* b_dst, const TopkWs& w,
+                 size_t ws_bytes, void* stream) {
+  if (n_cand == 0) return TGNX_OK;
   const int64_t ldh = ld_of(D);
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
-  ListWs w;
-  w.nc = std::max<int64_t>(1, ceil_div(max_len, TK_LCHUNK));
-  w.hs = reinterpret_cast<float*>(p + off);
-  off += align256((size_t)n_src * ldh * 4);
-  w.hd = reinterpret_cast<float*>(p + off);
-  off += align256((size_t)n_cand * ldh * 4);
-  w.pval = reinterpret_cast<float*>(p + off);
-  off += align256((size_t)n_src * w.nc * k * 4);
-  w.pidx = reinterpret_cast<int*>(p + off);
-  off += align256((size_t)n_src * w.nc * k * 4);
-  w.gemm = p + off;
-  w.used = off;
-  return w;
+  const size_t gbytes = ws_bytes - w.used;
+  const int rc =
+      tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
+  if (rc != TGNX_OK) return rc;
+  return tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
+}
+
+// out_val / out_idx = the k best of every source's nc partial lists (nc = 0: every slot is padding)
+int launch_merge(hipStream_t s, int64_t n_src, int64_t nc, int32_t k, const TopkWs& w, int32_t sigmoid, float* out_val,
+                 int64_t* out_idx) {
+  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src, (int)nc,
+                     (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_idx);
+  TGNX_LAUNCH_CHECK("topk_merge");
+  return TGNX_OK;
 }
 
 // the dense operator with or without exclusions (f == nullptr: the launches tgnx_link_predictor_topk always made)
@@ -765,13 +699,9 @@ int topk_dense(const char* name, int64_t n_src, int64_t n_cand, int64_t d_in, in
                const float* z_cand, const float* w_src, const float* b_src, const float* w_dst, const float* b_dst,
                const float* w_out, const float* b_out, int32_t k, int32_t sigmoid, const TopkFilter* f, float* out_val,
                int64_t* out_idx, float* out_all, void* ws, size_t ws_bytes, void* stream) {
-  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "%s: k must be in [1, %d], got %d", name, TGNX_TOPK_MAX, k);
-  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
-                     n_cand < (int64_t(1) << 31) - TK_CHUNK_MAX && n_src < (int64_t(1) << 31),
-                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
-  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && (n_src == 0 || (z_src && out_val && out_idx)) &&
-                     (n_cand == 0 || z_cand),
-                 "%s: null pointer", name);
+  int rc = check_common(name, n_src, n_cand, d_in, D, k, (int64_t(1) << 31) - TK_CHUNK_MAX, z_cand, w_src, w_dst, w_out,
+                        b_out, ws, n_src == 0 || (z_src && out_val && out_idx));
+  if (rc != TGNX_OK) return rc;
   if (f)
     TGNX_CHECK_ARG(f->nnz >= 0 && (!f->excl_ptr || f->nnz == 0 || f->excl_key),
                    "%s: excl_ptr needs excl_key and nnz >= 0", name);
@@ -779,17 +709,14 @@ int topk_dense(const char* name, int64_t n_src, int64_t n_cand, int64_t d_in, in
                  name);
   if (n_src == 0) return TGNX_OK;
   hipStream_t s = as_stream(stream);
-  const TopkWs w = topk_ws(ws, n_src, n_cand, D, k);
+  const TopkWs w = carve_ws(ws, n_src, n_cand, D, k, dense_lists(n_cand));
   const int64_t ldh = ld_of(D);
   const int chunk = chunk_of(n_src, n_cand);
   const int64_t nc = ceil_div(n_cand, chunk), blocks = ceil_div(n_src, TK_TQ) * nc;
   TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "%s: n_src x n_cand beyond one launch's grid", name);
-  if (n_cand > 0) {
-    const size_t gbytes = ws_bytes - w.used;
-    int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
-    if (rc != TGNX_OK) return rc;
-    rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
-    if (rc != TGNX_OK) return rc;
+  rc = project_rows(n_src, n_cand, d_in, D, z_src, z_cand, w_src, b_src, w_dst, b_dst, w, ws_bytes, stream);
+  if (rc != TGNX_OK) return rc;
+  if (n_cand > 0) {  // (n_cand = 0: no chunk)
     if (f)
       hipLaunchKernelGGL(topk_pairs<true>, dim3((unsigned)blocks), dim3(TK_BLOCK),
                          pairs_smem(ldh, chunk) + sizeof(TopkFilterLds), s, n_src, n_cand, (int)D, (int)ldh, chunk,
@@ -801,11 +728,7 @@ int topk_dense(const char* name, int64_t n_src, int64_t n_cand, int64_t d_in, in
                          (int)k, w.pval, w.pidx, out_all, TopkFilter{});
     TGNX_LAUNCH_CHECK("topk_pairs");
   }
-  // (n_cand = 0: no chunk, every slot is padding)
-  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src, (int)nc,
-                     (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_idx);
-  TGNX_LAUNCH_CHECK("topk_merge");
-  return TGNX_OK;
+  return launch_merge(s, n_src, nc, k, w, sigmoid, out_val, out_idx);
 }
 
 }  // namespace
@@ -814,10 +737,7 @@ extern "C" {
 
 size_t tgnx_link_predictor_topk_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, int32_t k) {
   if (n_src < 0 || n_cand < 0 || d_in <= 0 || D <= 0 || D > TK_DMAX || k < 1 || k > TGNX_TOPK_MAX) return 256;
-  const TopkWs w = topk_ws(nullptr, n_src, n_cand, D, k);
-  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
-                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
-  return w.used + align256(g) + 256;
+  return ws_bytes_of(n_src, n_cand, d_in, D, k, dense_lists(n_cand));
 }
 
 int tgnx_link_predictor_topk(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
@@ -848,10 +768,7 @@ size_t tgnx_link_predictor_topk_lists_ws_bytes(int64_t n_src, int64_t n_cand, in
                                                int64_t max_len) {
   if (n_src < 0 || n_cand < 0 || d_in <= 0 || D <= 0 || D > TK_DMAX || k < 1 || k > TGNX_TOPK_MAX || max_len < 0)
     return 256;
-  const ListWs w = list_ws(nullptr, n_src, n_cand, D, k, max_len);
-  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
-                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
-  return w.used + align256(g) + 256;
+  return ws_bytes_of(n_src, n_cand, d_in, D, k, list_chunks(max_len));
 }
 
 int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
@@ -861,38 +778,28 @@ int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, 
                                    int64_t max_len, float* out_val, int64_t* out_idx, int64_t* out_slot,
                                    float* out_logits, int64_t* n_invalid, void* ws, size_t ws_bytes, void* stream) {
   const char* name = "tgnx_link_predictor_topk_lists";
-  TGNX_CHECK_ARG(k >= 1 && k <= TGNX_TOPK_MAX, "%s: k must be in [1, %d], got %d", name, TGNX_TOPK_MAX, k);
-  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
-                     n_cand < (int64_t(1) << 31) && n_src < (int64_t(1) << 31),
-                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
+  int rc = check_common(name, n_src, n_cand, d_in, D, k, int64_t(1) << 31, z_cand, w_src, w_dst, w_out, b_out, ws,
+                        list_ptr && (nnz == 0 || list_idx) && (n_src == 0 || (z_src && out_val && out_idx && out_slot)));
+  if (rc != TGNX_OK) return rc;
   TGNX_CHECK_ARG(nnz >= 0 && max_len >= 0 && max_len < (int64_t(1) << 31) - TK_LCHUNK,
                  "%s: nnz and max_len must be >= 0 (max_len < 2^31 - %d)", name, TK_LCHUNK);
-  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws && list_ptr && (nnz == 0 || list_idx) &&
-                     (n_src == 0 || (z_src && out_val && out_idx && out_slot)) && (n_cand == 0 || z_cand),
-                 "%s: null pointer", name);
   TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_topk_lists_ws_bytes(n_src, n_cand, d_in, D, k, max_len),
                  "%s: workspace too small", name);
   if (n_src == 0) return TGNX_OK;
   hipStream_t s = as_stream(stream);
-  const ListWs w = list_ws(ws, n_src, n_cand, D, k, max_len);
-  const int64_t ldh = ld_of(D), blocks = n_src * w.nc;
+  const int64_t ldh = ld_of(D), nc = list_chunks(max_len), blocks = n_src * nc;
+  const TopkWs w = carve_ws(ws, n_src, n_cand, D, k, nc);
   TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "%s: n_src x max_len beyond one launch's grid", name);
-  if (n_cand > 0) {  // the dense operator's two GEMMs, the same shapes
-    const size_t gbytes = ws_bytes - w.used;
-    int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
-    if (rc != TGNX_OK) return rc;
-    rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
-    if (rc != TGNX_OK) return rc;
-  }
-  // (n_cand = 0: Hs is not computed and not used, every entry is skipped)
+  rc = project_rows(n_src, n_cand, d_in, D, z_src, z_cand, w_src, b_src, w_dst, b_dst, w, ws_bytes, stream);
+  if (rc != TGNX_OK) return rc;
+  // (n_cand = 0: every entry is skipped)
   hipLaunchKernelGGL(topk_list_pairs, dim3((unsigned)blocks), dim3(TK_LCHUNK), (size_t)(2 * ldh + TK_LCHUNK) * 4, s,
-                     n_cand, (int)D, (int)ldh, (int)w.nc, nnz, max_len, list_ptr, list_idx, (const float*)w.hs,
+                     n_cand, (int)D, (int)ldh, (int)nc, nnz, max_len, list_ptr, list_idx, (const float*)w.hs,
                      (const float*)w.hd, w_out, b_out, (int)k, w.pval, w.pidx, out_logits,
                      reinterpret_cast<unsigned long long*>(n_invalid));
   TGNX_LAUNCH_CHECK("topk_list_pairs");
-  hipLaunchKernelGGL(topk_merge, dim3((unsigned)ceil_div(n_src, TK_BLOCK / WAVE)), dim3(TK_BLOCK), 0, s, n_src,
-                     (int)w.nc, (int)k, (const float*)w.pval, (const int*)w.pidx, (int)sigmoid, out_val, out_slot);
-  TGNX_LAUNCH_CHECK("topk_merge");
+  rc = launch_merge(s, n_src, nc, k, w, sigmoid, out_val, out_slot);
+  if (rc != TGNX_OK) return rc;
   hipLaunchKernelGGL(topk_list_idx, dim3((unsigned)ceil_div(n_src * k, TK_BLOCK)), dim3(TK_BLOCK), 0, s, n_src, (int)k,
                      nnz, list_ptr, list_idx, (const int64_t*)out_slot, out_idx);
   TGNX_LAUNCH_CHECK("topk_list_idx");
@@ -901,10 +808,7 @@ int tgnx_link_predictor_topk_lists(int64_t n_src, int64_t n_cand, int64_t d_in, 
 
 size_t tgnx_link_predictor_rank_ws_bytes(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D) {
   if (n_src < 0 || n_cand < 0 || d_in <= 0 || D <= 0 || D > TK_DMAX) return 256;
-  const RankWs w = rank_ws(nullptr, n_src, n_cand, D);
-  const size_t g = std::max(n_src > 0 ? tgnx_gemm_f32_ws_bytes(n_src, D, d_in) : 0,
-                            n_cand > 0 ? tgnx_gemm_f32_ws_bytes(n_cand, D, d_in) : 0);
-  return w.used + align256(g) + 256;
+  return ws_bytes_of(n_src, n_cand, d_in, D, 1, 0);
 }
 
 int tgnx_link_predictor_rank(int64_t n_src, int64_t n_cand, int64_t d_in, int64_t D, const float* z_src,
@@ -915,32 +819,23 @@ int tgnx_link_predictor_rank(int64_t n_src, int64_t n_cand, int64_t d_in, int64_
                              int64_t* out_eq, int64_t* out_n, float* out_tlogit, void* ws, size_t ws_bytes,
                              void* stream) {
   const char* name = "tgnx_link_predictor_rank";
-  TGNX_CHECK_ARG(n_src >= 0 && n_cand >= 0 && d_in >= 1 && D >= 1 && D <= TK_DMAX && d_in < (1 << 30) &&
-                     n_cand < (int64_t(1) << 31) - TK_BLOCK && n_src < (int64_t(1) << 31),
-                 "%s: bad sizes (n_src, n_cand >= 0, d_in >= 1, 1 <= D <= %d)", name, (int)TK_DMAX);
+  int rc = check_common(name, n_src, n_cand, d_in, D, 1, (int64_t(1) << 31) - TK_BLOCK, z_cand, w_src, w_dst, w_out,
+                        b_out, ws, n_src == 0 || (z_src && target && out_gt && out_eq && out_n && out_tlogit));
+  if (rc != TGNX_OK) return rc;
   TGNX_CHECK_ARG(n_count >= 0 && n_count <= n_cand, "%s: n_count must be in [0, n_cand], got %lld", name,
                  (long long)n_count);
-  TGNX_CHECK_ARG(w_src && w_dst && w_out && b_out && ws &&
-                     (n_src == 0 || (z_src && target && out_gt && out_eq && out_n && out_tlogit)) &&
-                     (n_cand == 0 || z_cand),
-                 "%s: null pointer", name);
   TGNX_CHECK_ARG(nnz >= 0 && (!excl_ptr || nnz == 0 || excl_key), "%s: excl_ptr needs excl_key and nnz >= 0", name);
   TGNX_CHECK_ARG(ws_bytes >= tgnx_link_predictor_rank_ws_bytes(n_src, n_cand, d_in, D), "%s: workspace too small",
                  name);
   if (n_src == 0) return TGNX_OK;
   hipStream_t s = as_stream(stream);
-  const RankWs w = rank_ws(ws, n_src, n_cand, D);
+  const TopkWs w = carve_ws(ws, n_src, n_cand, D, 1, 0);
   const int64_t ldh = ld_of(D);
   const int64_t nc = ceil_div(n_count, TK_BLOCK), blocks = ceil_div(n_src, TK_TQ) * nc;
   TGNX_CHECK_ARG(blocks < (int64_t(1) << 31), "%s: n_src x n_count beyond one launch's grid", name);
-  if (n_cand > 0) {  // the dense operator's two GEMMs, the same shapes
-    const size_t gbytes = ws_bytes - w.used;
-    int rc = tgnx_gemm_f32(n_src, D, d_in, z_src, d_in, 0, w_src, d_in, 1, w.hs, ldh, b_src, 0, w.gemm, gbytes, stream);
-    if (rc != TGNX_OK) return rc;
-    rc = tgnx_gemm_f32(n_cand, D, d_in, z_cand, d_in, 0, w_dst, d_in, 1, w.hd, ldh, b_dst, 0, w.gemm, gbytes, stream);
-    if (rc != TGNX_OK) return rc;
-  }
-  // (n_cand = 0: Hs is not computed and not used, every row is skipped)
+  rc = project_rows(n_src, n_cand, d_in, D, z_src, z_cand, w_src, b_src, w_dst, b_dst, w, ws_bytes, stream);
+  if (rc != TGNX_OK) return rc;
+  // (n_cand = 0: every row is skipped)
   unsigned long long* gt = reinterpret_cast<unsigned long long*>(out_gt);
   unsigned long long* eq = reinterpret_cast<unsigned long long*>(out_eq);
   unsigned long long* nn = reinterpret_cast<unsigned long long*>(out_n);

@@ -328,44 +328,7 @@ at::Tensor predictor(const at::Tensor& z_src, const at::Tensor& z_dst, const at:
   return out;
 }
 
-// LinkPredictor over all (source, candidate) pairs with the top-k selection fused in (csrc/tgnx_topk.hip):
-// (val [B, k], idx [B, k] positions into z_cand, logits [B, C] or an empty tensor)
-std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk(
-    const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src,
-    const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out,
-    int64_t k, bool sigmoid, bool return_scores) {
-  dev_tensor(z_src, at::kFloat, "z_src");
-  dev_tensor(z_cand, at::kFloat, "z_cand");
-  dev_tensor(w_src, at::kFloat, "w_src");
-  dev_tensor(w_dst, at::kFloat, "w_dst");
-  dev_tensor(w_out, at::kFloat, "w_out");
-  dev_tensor(b_out, at::kFloat, "b_out");
-  TORCH_CHECK(z_src.dim() == 2 && z_cand.dim() == 2 && z_src.size(1) == z_cand.size(1), "z_src [B, d] and z_cand [C, d]");
-  const int64_t B = z_src.size(0), C = z_cand.size(0), d_in = z_src.size(1), D = w_src.size(0);
-  TORCH_CHECK(w_src.dim() == 2 && w_src.size(1) == d_in && w_dst.dim() == 2 && w_dst.size(0) == D &&
-                  w_dst.size(1) == d_in,
-              "w_src / w_dst must be [D, d]");
-  TORCH_CHECK(w_out.numel() == D && b_out.numel() == 1, "w_out must have D entries and b_out one");
-  TORCH_CHECK(k >= 1 && k <= TGNX_TOPK_MAX, "k must be in [1, ", TGNX_TOPK_MAX, "], got ", k);
-  same_device(z_src, {&z_cand, &w_src, &w_dst, &w_out, &b_out});
-  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
-  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
-  const c10::OptionalDeviceGuard guard(z_src.device());
-  at::Tensor val = at::empty({B, k}, z_src.options());
-  at::Tensor idx = at::empty({B, k}, z_src.options().dtype(at::kLong));
-  at::Tensor all = return_scores ? at::empty({B, C}, z_src.options()) : at::empty({0}, z_src.options());
-  const size_t nb = tgnx_link_predictor_topk_ws_bytes(B, C, d_in, D, (int32_t)k);
-  at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
-  check_rc(tgnx_link_predictor_topk(B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(),
-                                    w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(),
-                                    b_out.data_ptr<float>(), (int32_t)k, sigmoid ? 1 : 0, val.data_ptr<float>(),
-                                    idx.data_ptr<int64_t>(), return_scores ? all.data_ptr<float>() : nullptr,
-                                    ws.data_ptr(), nb, cur_stream()),
-           "tgnx_link_predictor_topk");
-  return {val, idx, all};
-}
-
-// the argument checks predictor_topk makes, shared by its filtered and per-source-list forms; returns (d_in, D)
+// the argument checks of the top-k and rank ops (csrc/tgnx_topk.hip); returns (d_in, D)
 std::pair<int64_t, int64_t> topk_args(const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src,
                                       const at::Tensor& w_dst, const at::Tensor& w_out, const at::Tensor& b_out,
                                       int64_t k) {
@@ -386,12 +349,59 @@ std::pair<int64_t, int64_t> topk_args(const at::Tensor& z_src, const at::Tensor&
   return {d_in, D};
 }
 
+// the dense ops' outputs: (val [B, k], idx [B, k], logits [B, C] or an empty tensor)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> topk_outputs(const at::Tensor& z_src, int64_t C, int64_t k,
+                                                            bool return_scores) {
+  const int64_t B = z_src.size(0);
+  return {at::empty({B, k}, z_src.options()), at::empty({B, k}, z_src.options().dtype(at::kLong)),
+          return_scores ? at::empty({B, C}, z_src.options()) : at::empty({0}, z_src.options())};
+}
+
 const int64_t* opt_long(const c10::optional<at::Tensor>& x, const at::Tensor& ref, int64_t numel, const char* name) {
   if (!x.has_value()) return nullptr;
   dev_tensor(*x, at::kLong, name);
   TORCH_CHECK(numel < 0 || x->numel() == numel, name, " must have ", numel, " entries");
   same_device(ref, {&*x});
   return x->data_ptr<int64_t>();
+}
+
+// the exclusion-by-key arguments of the filtered top-k and the rank op, checked: the C ABI's four pointers and nnz
+struct KeyArgs {
+  const int64_t *cand_key, *src_key, *excl_ptr, *excl_key;
+  int64_t nnz;
+};
+KeyArgs key_args(const at::Tensor& z_src, int64_t C, const c10::optional<at::Tensor>& cand_key,
+                 const c10::optional<at::Tensor>& src_key, const c10::optional<at::Tensor>& excl_ptr,
+                 const c10::optional<at::Tensor>& excl_key) {
+  const int64_t B = z_src.size(0);
+  const KeyArgs a{opt_long(cand_key, z_src, C, "cand_key"), opt_long(src_key, z_src, B, "src_key"),  // (in this order)
+                  opt_long(excl_ptr, z_src, B + 1, "excl_ptr"), opt_long(excl_key, z_src, -1, "excl_key"),
+                  excl_key.has_value() ? excl_key->numel() : 0};
+  TORCH_CHECK(!a.excl_ptr || excl_key.has_value(), "excl_ptr needs excl_key");
+  return a;
+}
+
+// LinkPredictor over all (source, candidate) pairs with the top-k selection fused in (csrc/tgnx_topk.hip):
+// (val [B, k], idx [B, k] positions into z_cand, logits [B, C] or an empty tensor)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk(
+    const at::Tensor& z_src, const at::Tensor& z_cand, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src,
+    const at::Tensor& w_dst, const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out,
+    int64_t k, bool sigmoid, bool return_scores) {
+  const auto [d_in, D] = topk_args(z_src, z_cand, w_src, w_dst, w_out, b_out, k);
+  const int64_t B = z_src.size(0), C = z_cand.size(0);
+  const float* bs = opt_ptr(b_src, z_src, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
+  const c10::OptionalDeviceGuard guard(z_src.device());
+  auto [val, idx, all] = topk_outputs(z_src, C, k, return_scores);
+  const size_t nb = tgnx_link_predictor_topk_ws_bytes(B, C, d_in, D, (int32_t)k);
+  at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
+  check_rc(tgnx_link_predictor_topk(B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(),
+                                    w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(),
+                                    b_out.data_ptr<float>(), (int32_t)k, sigmoid ? 1 : 0, val.data_ptr<float>(),
+                                    idx.data_ptr<int64_t>(), return_scores ? all.data_ptr<float>() : nullptr,
+                                    ws.data_ptr(), nb, cur_stream()),
+           "tgnx_link_predictor_topk");
+  return {val, idx, all};
 }
 
 // predictor_topk with per-source exclusions by key (tgnx_link_predictor_topk_filtered); the logits are unmasked
@@ -405,23 +415,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk_filtered(
   const int64_t B = z_src.size(0), C = z_cand.size(0);
   const float* bs = opt_ptr(b_src, z_src, D, "b_src");
   const float* bd = opt_ptr(b_dst, z_src, D, "b_dst");
-  const int64_t* ck = opt_long(cand_key, z_src, C, "cand_key");
-  const int64_t* sk = opt_long(src_key, z_src, B, "src_key");
-  const int64_t* ep = opt_long(excl_ptr, z_src, B + 1, "excl_ptr");
-  const int64_t* ek = opt_long(excl_key, z_src, -1, "excl_key");
-  TORCH_CHECK(!ep || excl_key.has_value(), "excl_ptr needs excl_key");
-  const int64_t nnz = excl_key.has_value() ? excl_key->numel() : 0;
+  const KeyArgs f = key_args(z_src, C, cand_key, src_key, excl_ptr, excl_key);
   const c10::OptionalDeviceGuard guard(z_src.device());
-  at::Tensor val = at::empty({B, k}, z_src.options());
-  at::Tensor idx = at::empty({B, k}, z_src.options().dtype(at::kLong));
-  at::Tensor all = return_scores ? at::empty({B, C}, z_src.options()) : at::empty({0}, z_src.options());
+  auto [val, idx, all] = topk_outputs(z_src, C, k, return_scores);
   const size_t nb = tgnx_link_predictor_topk_filtered_ws_bytes(B, C, d_in, D, (int32_t)k);
   at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
   check_rc(tgnx_link_predictor_topk_filtered(
                B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(), w_src.data_ptr<float>(), bs,
                w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(), b_out.data_ptr<float>(), (int32_t)k,
-               sigmoid ? 1 : 0, ck, sk, ep, ek, nnz, val.data_ptr<float>(), idx.data_ptr<int64_t>(),
-               return_scores ? all.data_ptr<float>() : nullptr, ws.data_ptr(), nb, cur_stream()),
+               sigmoid ? 1 : 0, f.cand_key, f.src_key, f.excl_ptr, f.excl_key, f.nnz, val.data_ptr<float>(),
+               idx.data_ptr<int64_t>(), return_scores ? all.data_ptr<float>() : nullptr, ws.data_ptr(), nb,
+               cur_stream()),
            "tgnx_link_predictor_topk_filtered");
   return {val, idx, all};
 }
@@ -477,12 +481,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_rank(
   dev_tensor(target, at::kLong, "target");
   TORCH_CHECK(target.numel() == B, "target must have n_src entries");
   same_device(z_src, {&target});
-  const int64_t* ck = opt_long(cand_key, z_src, C, "cand_key");
-  const int64_t* sk = opt_long(src_key, z_src, B, "src_key");
-  const int64_t* ep = opt_long(excl_ptr, z_src, B + 1, "excl_ptr");
-  const int64_t* ek = opt_long(excl_key, z_src, -1, "excl_key");
-  TORCH_CHECK(!ep || excl_key.has_value(), "excl_ptr needs excl_key");
-  const int64_t nnz = excl_key.has_value() ? excl_key->numel() : 0;
+  const KeyArgs f = key_args(z_src, C, cand_key, src_key, excl_ptr, excl_key);
   const c10::OptionalDeviceGuard guard(z_src.device());
   const auto lopt = z_src.options().dtype(at::kLong);
   at::Tensor gt = at::empty({B}, lopt), eq = at::empty({B}, lopt), n = at::empty({B}, lopt);
@@ -491,9 +490,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_rank(
   at::Tensor ws = at::empty({(int64_t)nb}, z_src.options().dtype(at::kByte));
   check_rc(tgnx_link_predictor_rank(B, C, d_in, D, z_src.data_ptr<float>(), z_cand.data_ptr<float>(),
                                     w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(),
-                                    b_out.data_ptr<float>(), n_count, target.data_ptr<int64_t>(), ck, sk, ep, ek, nnz,
-                                    gt.data_ptr<int64_t>(), eq.data_ptr<int64_t>(), n.data_ptr<int64_t>(),
-                                    tl.data_ptr<float>(), ws.data_ptr(), nb, cur_stream()),
+                                    b_out.data_ptr<float>(), n_count, target.data_ptr<int64_t>(), f.cand_key, f.src_key,
+                                    f.excl_ptr, f.excl_key, f.nnz, gt.data_ptr<int64_t>(), eq.data_ptr<int64_t>(),
+                                    n.data_ptr<int64_t>(), tl.data_ptr<float>(), ws.data_ptr(), nb, cur_stream()),
            "tgnx_link_predictor_rank");
   return {gt, eq, n, tl};
 }

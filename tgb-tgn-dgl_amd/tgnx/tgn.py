@@ -1238,6 +1238,28 @@ class TgnEngine:
             self.check()
         return out
 
+    def _ids(self, x) -> torch.Tensor:
+        """Node ids (any integer sequence / tensor) as a flat contiguous int64 tensor on the device."""
+        return torch.as_tensor(x).to(self.dev, torch.long).contiguous().view(-1)
+
+    def _candidates(self, candidates) -> torch.Tensor:
+        """The candidate node ids of a query: the caller's, else the engine's dst_nodes, else every node."""
+        if candidates is None:
+            candidates = self.dst_nodes if self.dst_nodes is not None else \
+                torch.arange(self.cfg.num_nodes, device=self.dev)
+        return self._ids(candidates)
+
+    def _link_weights(self):
+        """The model's link_pred parameters in the order the link operators take them."""
+        lp = self.model.link_pred
+        return (lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight,
+                lp.lin_final.bias)
+
+    @staticmethod
+    def _node_ids(idx, table):
+        """Selected positions into `table` as node ids; the padding (-1) stays."""
+        return torch.where(idx >= 0, table[idx.clamp(min=0)], idx) if table.numel() else idx
+
     @torch.no_grad()
     def recommend(self, src, k: int, candidates=None, return_scores: bool = False):
         """For every source node the k candidates the model ranks highest at the current stream state:
@@ -1247,19 +1269,11 @@ class TgnEngine:
         (ops.link_topk: ranked by logit, equal logits by the candidate's position in `candidates`).  k beyond the
         candidate count pads with node id -1 and val 0."""
         from . import ops
-        if candidates is None:
-            candidates = self.dst_nodes if self.dst_nodes is not None else \
-                torch.arange(self.cfg.num_nodes, device=self.dev)
-        cand = torch.as_tensor(candidates).to(self.dev, torch.long).contiguous().view(-1)
-        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        cand, src = self._candidates(candidates), self._ids(src)
         z = self.embed(torch.cat([src, cand]))
-        lp = self.model.link_pred
-        out = ops.link_topk(z[:src.numel()], z[src.numel():], lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight,
-                            lp.lin_dst.bias, lp.lin_final.weight, lp.lin_final.bias, k, sigmoid=True,
+        out = ops.link_topk(z[:src.numel()], z[src.numel():], *self._link_weights(), k, sigmoid=True,
                             return_scores=return_scores)
-        idx = out[1]
-        ids = torch.where(idx >= 0, cand[idx.clamp(min=0)], idx) if cand.numel() else idx
-        return (out[0], ids) + tuple(out[2:])
+        return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
 
     def _ragged_ids(self, x, n_src, what):
         """(ptr [n_src + 1], node ids, longest segment) on the device from a (ptr, ids) tuple of tensors / arrays or a
@@ -1318,13 +1332,11 @@ class TgnEngine:
         private copy.  Returns (val [Q, k], node_ids [Q, k][, logits [nnz]]), the logits aligned with the caller's
         entries and NaN at an excluded one."""
         from . import ops
-        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
+        src = self._ids(src)
         Q, N = src.numel(), self.cfg.num_nodes
         if Q and bool(((src < 0) | (src >= N)).any()):
             raise ValueError(f"recommend: node ids must be in [0, {N})")
-        lp = self.model.link_pred
-        w = (lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight,
-             lp.lin_final.bias)
+        w = self._link_weights()
         ex = self._exclusions(src, exclude_seen, exclude)
         if per_source is not None:
             if candidates is not None:
@@ -1342,39 +1354,29 @@ class TgnEngine:
                 pos[ex[2][at] == comp] = -1
             out = ops.link_topk(z[:Q], z[Q:], *w, k, sigmoid=True, return_scores=return_scores, lists=(ptr, pos),
                                 validate=False, max_len=longest)
-            idx = out[1]
-            node = torch.where(idx >= 0, uniq[idx.clamp(min=0)], idx) if uniq.numel() else idx
-            return (out[0], node) + tuple(out[3:])
+            return (out[0], self._node_ids(out[1], uniq)) + tuple(out[3:])
         if ex is None and not exclude_self:
             return self.recommend(src, k, candidates=candidates, return_scores=return_scores)
-        if candidates is None:
-            candidates = self.dst_nodes if self.dst_nodes is not None else torch.arange(N, device=self.dev)
-        cand = torch.as_tensor(candidates).to(self.dev, torch.long).contiguous().view(-1)
+        cand = self._candidates(candidates)
         z = self.embed(torch.cat([src, cand]))
         out = ops.link_topk(z[:Q], z[Q:], *w, k, sigmoid=True, return_scores=return_scores, cand_key=cand,
                             src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2],
                             validate=False)
-        idx = out[1]
-        ids = torch.where(idx >= 0, cand[idx.clamp(min=0)], idx) if cand.numel() else idx
-        return (out[0], ids) + tuple(out[2:])
+        return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
 
     @torch.no_grad()
     def score(self, src, dst) -> torch.Tensor:
         """The model's link probability [n] for the explicit pairs (src[i], dst[i]) at the current stream state:
         embed() of both lists, then the LinkPredictor operator.  Read-only as embed() is."""
         from . import ops
-        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
-        dst = torch.as_tensor(dst).to(self.dev, torch.long).contiguous().view(-1)
+        src, dst = self._ids(src), self._ids(dst)
         if src.numel() != dst.numel():
             raise ValueError(f"score: {src.numel()} sources for {dst.numel()} destinations")
         n = src.numel()
         z = self.embed(torch.cat([src, dst]))
         if n == 0:
             return z.new_empty(0)
-        lp = self.model.link_pred
-        return ops.link_predictor(z[:n].contiguous(), z[n:].contiguous(), lp.lin_src.weight, lp.lin_src.bias,
-                                  lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight, lp.lin_final.bias,
-                                  sigmoid=True).view(-1)
+        return ops.link_predictor(z[:n].contiguous(), z[n:].contiguous(), *self._link_weights(), sigmoid=True).view(-1)
 
     @torch.no_grad()
     def rank(self, src, dst, candidates=None, return_scores: bool = False, *, exclude_seen: bool = False,
@@ -1389,22 +1391,17 @@ class TgnEngine:
         once with embed(); the counts come from one fused pass (ops.link_rank), no [Q, C] logits unless asked for.
         Read-only as recommend() is."""
         from . import ops
-        src = torch.as_tensor(src).to(self.dev, torch.long).contiguous().view(-1)
-        dst = torch.as_tensor(dst).to(self.dev, torch.long).contiguous().view(-1)
+        src, dst = self._ids(src), self._ids(dst)
         Q, N = src.numel(), self.cfg.num_nodes
         if dst.numel() != Q:
             raise ValueError(f"rank: {Q} sources for {dst.numel()} destinations")
         if Q and bool(((src < 0) | (src >= N) | (dst < 0) | (dst >= N)).any()):
             raise ValueError(f"rank: node ids must be in [0, {N})")
-        if candidates is None:
-            candidates = self.dst_nodes if self.dst_nodes is not None else torch.arange(N, device=self.dev)
-        cand = torch.as_tensor(candidates).to(self.dev, torch.long).contiguous().view(-1)
+        cand = self._candidates(candidates)
         C = cand.numel()
         ex = self._exclusions(src, exclude_seen, exclude)
         z = self.embed(torch.cat([src, cand, dst]))
-        lp = self.model.link_pred
-        w = (lp.lin_src.weight, lp.lin_src.bias, lp.lin_dst.weight, lp.lin_dst.bias, lp.lin_final.weight,
-             lp.lin_final.bias)
+        w = self._link_weights()
         rank, gt, eq, n, tlogit = ops.link_rank(
             z[:Q], z[Q:], *w, C + torch.arange(Q, device=self.dev), n_count=C, cand_key=torch.cat([cand, dst]),
             src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2], validate=False)
