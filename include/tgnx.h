@@ -562,6 +562,43 @@ int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, cons
  * Test: tests/test_gpu_tgn_observe.py (against the eval step bit for bit, and against the oracle's update_state). */
 int tgnx_tgn_observe_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, void* stream);
 
+/* The embedding table (csrc/tgnx_embtab.hip): a materialised table[num_nodes, mem_dim] of what
+ * tgnx_tgn_embed returns, kept current by recomputing only the rows a batch made stale.  In eval mode the embedding of
+ * v is a function of v's memory / last_update and ring row, of the memory / last_update of the nodes in that row (and of
+ * their ring rows at layers = 2) and of immutable event rows; no query time enters.  With T the nodes whose memory,
+ * last_update or ring row was written since the table was current (the endpoints of every observed / evaluated batch)
+ * and ring(v) the entries of v's ring row with e_id >= 0 (reset_state leaves stale ids under e_id = -1):
+ *   D1 = { v : ring(v) meets T },  D2 = { v : ring(v) meets T | D1 },
+ *   stale = T | D1 at layers = 1,  T | D1 | D2 at layers = 2,
+ * evaluated on the ring as it stands when the list is made (an untouched node's row is what it was, a touched node is
+ * in T itself).  flags: uint8 planes [3][N] for T, D1, D2 (plane p at flags + p * N, N the node count of the call; a
+ * caller whose N grows re-lays them), zero when nothing is stale.  Every flag write is an idempotent plain store: no
+ * atomics, no read-modify-write of a shared byte.  One device only: the calls that take buf refuse a data-parallel
+ * engine's buffers (buf->xrows set) with TGNX_EINVAL.  No host synchronisation, no allocation.
+ * Test: tests/test_gpu_embtab.py (ids against a numpy restatement of the rule, rows against the oracle).
+ *
+ * tgnx_embtab_touch (1 launch): T[src[i]] = T[dst[i]] = 1 for i < B, one thread per endpoint; an id outside [0, N) is
+ * skipped.  B = 0 does nothing.
+ * tgnx_embtab_expand (1 launch, 2 at layers = 2): walks the ring [N, K] flat over (node, slot), reads T and writes D1,
+ * then reads T | D1 and writes D2; no pass reads the plane it writes.  D1 / D2 must be zero on entry (the list call
+ * leaves them so).
+ * tgnx_embtab_list (3 launches): out_ids = the ascending ids with any plane set (capacity N), *out_count (device
+ * int64) their number; all three planes are cleared.  The order comes from a fixed-order scan (wave ballot / popcount,
+ * then a scan of the workgroups' counts), so the list is run-to-run identical.  ws: tgnx_embtab_list_ws_bytes(N)
+ * bytes, 4-B aligned, not zeroed.  N >= 2^31: TGNX_ETOOBIG.
+ * tgnx_tgn_embed_into: tgnx_tgn_embed whose last launch writes the row of nodes[i] to table[nodes[i]] instead of
+ * out_z[i]: same launches, same capacity rule (n <= tgnx_tgn_embed_max_nodes), same private control-block copy, same
+ * read-only guarantees (GEN advances, ERR may take the overflow bit, and the listed rows are then zero-filled).  nodes
+ * must hold no duplicates (two waves would write one row; equal values, but unordered) — the list call's output has
+ * none; an id outside [0, num_nodes) writes nothing.  table has at least num_nodes rows. */
+int tgnx_embtab_touch(const int64_t* src, const int64_t* dst, int64_t B, int64_t N, uint8_t* flags, void* stream);
+int tgnx_embtab_expand(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, uint8_t* flags, void* stream);
+size_t tgnx_embtab_list_ws_bytes(int64_t N);
+int tgnx_embtab_list(uint8_t* flags, int64_t N, int32_t layers, int64_t* out_ids, int64_t* out_count, void* ws,
+                     size_t ws_bytes, void* stream);
+int tgnx_tgn_embed_into(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                        float* table /* [>= num_nodes, mem_dim] */, void* stream);
+
 /* Event-table compaction (csrc/tgnx_compact.hip): retire every row of the event table that nothing
  * references and renumber the survivors order-preservingly (new id = rank among the live rows).  A row e of the
  * num_events valid rows (cfg->num_events is the capacity) is live when a ring slot with nbr != -1 holds it, when a

@@ -4726,16 +4726,21 @@ __global__ void __launch_bounds__(256) tgn_score(Ctx c) {
   if (tid == 0) c.mrr[i] = 1.0 / (0.5 * ((double)cnt2[0] + (double)cnt2[1]) + 1.0);
 }
 
-// tgnx_tgn_embed's last launch (c: the root level's view, c.ctl the private copy): a wave per output row
+// tgnx_tgn_embed's last launch (c: the root level's view, c.ctl the private copy): a wave per output row.
+// INTO (tgnx_tgn_embed_into): the row of nodes[i] goes to out_z[nodes[i]] (a table indexed by node id; the list has
+// no duplicates, so no two waves write one row), and an id outside [0, N) writes nothing.
+template <bool INTO>
 __global__ void __launch_bounds__(256) tgn_embed_gather(Ctx c, int64_t* live_ctl, const int64_t* nodes, int n, float* out_z) {
   const int64_t err = c.ctl[TGNX_CTL_ERR];
   if (blockIdx.x == 0 && threadIdx.x == 0 && err != live_ctl[TGNX_CTL_ERR]) live_ctl[TGNX_CTL_ERR] |= err;
   const int lane = threadIdx.x & 63, D = c.D;
   for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
     const int64_t v = nodes[i];
-    const bool ok = err == 0 && v >= 0 && v < c.N;
+    const bool valid = v >= 0 && v < c.N, ok = err == 0 && valid;
+    if (INTO && !valid) continue;
     const float* z = ok ? c.Zc + (int64_t)root_row(c, v) * c.HC : nullptr;
-    for (int k = lane; k < D; k += WAVE) out_z[(int64_t)i * D + k] = ok ? z[k] : 0.f;
+    const int64_t row = INTO ? v : i;
+    for (int k = lane; k < D; k += WAVE) out_z[row * D + k] = ok ? z[k] : 0.f;
   }
 }
 
@@ -6080,18 +6085,20 @@ int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg) {
   if (check_cfg(cfg)) return 0;
   return make_caps(cfg).R1cap;
 }
-int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
-                   float* out_z, int64_t* n_invalid, void* stream) {
+// into: out_z is a table indexed by node id (tgnx_tgn_embed_into); else row i is nodes[i]'s
+static int embed_impl(const char* who, const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes,
+                      int64_t n, float* out_z, int64_t* n_invalid, bool into, void* stream) {
   Ctx c;
   Caps k;
   WsLay W;
-  TGNX_CHECK_ARG(cfg && buf, "tgnx_tgn_embed: null config or buffers");
+  TGNX_CHECK_ARG(cfg && buf, "%s: null config or buffers", who);
+  TGNX_CHECK_ARG(!into || !buf->xrows, "%s: one device only (buf->xrows set: a data-parallel engine)", who);
   int rc = make_ctx(cfg, buf, cfg->max_neg < 1 ? 1 : cfg->max_neg, c, k, W);
   if (rc) return rc;
-  TGNX_CHECK_ARG(n >= 0 && n <= k.R1cap, "tgnx_tgn_embed: n = %lld beyond tgnx_tgn_embed_max_nodes = %d", (long long)n,
+  TGNX_CHECK_ARG(n >= 0 && n <= k.R1cap, "%s: n = %lld beyond tgnx_tgn_embed_max_nodes = %d", who, (long long)n,
                  k.R1cap);
   if (n == 0) return TGNX_OK;
-  TGNX_CHECK_ARG(nodes && out_z, "tgnx_tgn_embed: null pointer");
+  TGNX_CHECK_ARG(nodes && out_z, "%s: null pointer", who);
   hipStream_t s = as_stream(stream);
   char* ws = reinterpret_cast<char*>(buf->ws);
   int* own = reinterpret_cast<int*>(ws + W.own);
@@ -6107,9 +6114,20 @@ int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, cons
   // role 0 alone: roles >= 1 build the insert / store plans of a batch's events, and there is no batch
   Ctx cr;
   if ((rc = infer_forward(s, c, k, k.R1cap, 1, cr))) return rc;
-  tgn_embed_gather<<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
+  if (into)
+    tgn_embed_gather<true><<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
+  else
+    tgn_embed_gather<false><<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
   TGNX_LAUNCH_CHECK("tgn_embed_gather");
   return TGNX_OK;
+}
+int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                   float* out_z, int64_t* n_invalid, void* stream) {
+  return embed_impl("tgnx_tgn_embed", cfg, buf, nodes, n, out_z, n_invalid, false, stream);
+}
+int tgnx_tgn_embed_into(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                        float* table, void* stream) {
+  return embed_impl("tgnx_tgn_embed_into", cfg, buf, nodes, n, table, nullptr, true, stream);
 }
 
 // eval_step_impl's state update without its forward: see tgn_observe_mark

@@ -4,3 +4,4 @@ from tgnx.tgn_epoch import compact, load_stream, observe, recommend, save_stream
 from tgnx.tgn_epoch import recommend_filtered  # noqa: F401
 from tgnx.tgn_epoch import rank_stream  # noqa: F401
 from tgnx.tgn_epoch import grow_nodes, observe_grow  # noqa: F401
+from tgnx.tgn_epoch import embedding_table  # noqa: F401

@@ -61,6 +61,12 @@ SIGNATURES = {
     "tgnx_tgn_embed_max_nodes": (c_i64, [P]),
     "tgnx_tgn_embed": (ctypes.c_int, [P, P, P, c_i64, P, P, c_vp]),
     "tgnx_tgn_observe_step": (ctypes.c_int, [P, P, c_vp]),
+    # the embedding table's stale-row bookkeeping (tgnx_embtab.hip) and its refresh
+    "tgnx_embtab_touch": (ctypes.c_int, [P, P, c_i64, c_i64, P, c_vp]),
+    "tgnx_embtab_expand": (ctypes.c_int, [P, P, P, c_vp]),
+    "tgnx_embtab_list_ws_bytes": (c_sz, [c_i64]),
+    "tgnx_embtab_list": (ctypes.c_int, [P, c_i64, c_i32, P, P, P, c_sz, c_vp]),
+    "tgnx_tgn_embed_into": (ctypes.c_int, [P, P, P, c_i64, P, c_vp]),
     "tgnx_tgn_compact_ws_bytes": (c_sz, [P, c_i64]),
     "tgnx_tgn_compact_plan": (ctypes.c_int, [P, P, c_i64, c_i64, P, c_sz, c_vp]),
     "tgnx_tgn_compact_apply": (ctypes.c_int, [P, P, c_i64, c_i64, P, P, P, P, P, P, c_i64, P, c_sz, c_vp]),

@@ -192,6 +192,8 @@ class TGNModel(nn.Module):
         self.store = None
         self.ensure_events(max(int(num_events or 0), 1))
         self.node_gen = torch.zeros(num_nodes, dtype=torch.int32, device=dev)
+        # bumped by every parameter load: an engine's embedding table compares it at refresh
+        self._param_version = 0
 
     def ensure_events(self, n: int) -> None:
         """Size the message-store arena for an event table of n rows (the reference's getModel does
@@ -262,6 +264,7 @@ class TGNModel(nn.Module):
         with torch.no_grad():
             for name, (o, n, _) in self._views.items():
                 self.flat[o:o + n].copy_(sd[name].reshape(-1).to(self.flat.device))
+        self._param_version += 1
 
     def grads_by_name(self) -> dict:
         """The last step's gradient of every parameter tensor (views into grad_flat).  Raises while an engine runs
@@ -297,6 +300,7 @@ class TGNModel(nn.Module):
         self.settle()
         out = super().load_state_dict(*a, **k)
         self.invalidate_prefetch()
+        self._param_version += 1
         return out
 
     def forward(self, *a, **k):
@@ -669,6 +673,12 @@ class TgnEngine:
         # (single step, group size, group), held apart from the train graphs
         self._ev = None
         self._ev_graphs = None
+        # the embedding table (enable_embedding_table; off by default): [node_capacity, D] current embeddings, the
+        # stale planes T / D1 / D2 (tgnx_embtab.hip), `_emb_all` = every row is stale (set by every call that moves
+        # state the host does not see batch by batch), and the (parameter, loader) versions the table was made at
+        self._emb_tab = None
+        self._emb_all = True
+        self._emb_ver = None
         if optimizer is None:
             self.adam_m, self.adam_v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
         else:
@@ -758,6 +768,7 @@ class TgnEngine:
     def reset_state(self):
         """memory_module.reset_state + neighbor_loader.reset_state (pyg_epoch_utils.py:15-16)."""
         self._settle()
+        self._emb_all = True
         b = self._buffers(0)
         _lib.call("tgnx_tgn_reset_state", ctypes.byref(self.cfg), ctypes.byref(b), self._stream())
         self.loader.reset_state()
@@ -765,6 +776,7 @@ class TgnEngine:
     def flush(self):
         """TGNMemory.train(False) (memory_module.py:209-215)."""
         self._settle()
+        self._emb_all = True
         b = self._buffers(0)
         nb = int(_lib.lib().tgnx_tgn_flush_scratch_bytes(ctypes.byref(self.cfg)))
         # graphs beyond one workspace chunk: a snapshot of memory / last_update.  It is allocated on, and
@@ -780,6 +792,7 @@ class TgnEngine:
         if neg is not None:
             self.neg_train[start:start + B].copy_(torch.as_tensor(neg).to(self.dev, torch.long))
         self.advance(start, B, True)
+        self._emb_all = True
         b = self._buffers(_p(self.neg_train))
         fused = update and self._fused()
         _lib.call("tgnx_tgn_train_step" if fused else "tgnx_tgn_train_fwd_bwd", ctypes.byref(self.cfg), ctypes.byref(b),
@@ -795,6 +808,7 @@ class TgnEngine:
         return self.fuse_adam and not self.dp
 
     def apply_update(self, allreduce: bool = True):
+        self._emb_all = True
         if allreduce and self.dp:
             self._exchange()
         if self.dp:   # the exchanged rows and Adam in one launch
@@ -824,6 +838,7 @@ class TgnEngine:
         # the kernels index neg[(start + i) * Kn + c]: shift the base pointer by start rows
         b = self._buffers(negs.data_ptr() - start * Kn * 8)
         _lib.call("tgnx_tgn_eval_step", ctypes.byref(self.cfg), ctypes.byref(b), Kn, self._stream())
+        self._emb_touch(start, B)
         self._keep = negs
         return self.out_pos[:B], self.out_neg[:B * Kn].view(B, Kn), self.mrr[:B]
 
@@ -912,8 +927,10 @@ class TgnEngine:
                 tuple(new[k] for k in ("memory", "last_update", "node_gen"))
         else:
             ring, node = ld._alloc, m._node_alloc
+        lv = getattr(ld, "version", None)
         ld._install(*ring, n)
         m._install_nodes(*node, new.get("store", m.store), n)
+        self._emb_moved(N, lv)
         if n > N:   # the workspace's layout follows num_nodes: a fresh one (scratch only: zero = initial state)
             self.ws = torch.zeros(nb, dtype=torch.uint8, device=self.dev)
         self._prefetched = False
@@ -1015,6 +1032,7 @@ class TgnEngine:
         b = self._buffers(0)
         b.xrows, b.xcap = 0, 0
         _lib.call("tgnx_tgn_observe_step", ctypes.byref(self.cfg), ctypes.byref(b), self._stream())
+        self._emb_touch(start, B)
 
     def observe_range(self, lo: int, hi: int, batch=None):
         """observe() over resident rows [lo, hi) in batches of `batch` (default cfg.max_batch), the last one partial:
@@ -1121,7 +1139,10 @@ class TgnEngine:
         engine's (their RNG offset is the batch's CUR_EID).  The old and new tables coexist until this returns.
 
         An event id outside [0, num_events) in the ring or a store is counted on the device, never dereferenced:
-        RuntimeError, with the engine untouched.  One device only (ValueError at world > 1).  One host read."""
+        RuntimeError, with the engine untouched.  One device only (ValueError at world > 1).  One host read.
+
+        The embedding table (enable_embedding_table) stays current: ids are renumbered, but every ring slot and store
+        entry names a row with the same t and msg values, and an embedding reads values, not ids: nothing goes stale."""
         upto = check_compact_args(self.num_events, upto, capacity, self.world)
         if self.dp:
             raise ValueError("compact_events: one device only (the data-parallel step forms are not built)")
@@ -1135,7 +1156,10 @@ class TgnEngine:
                                "twice in one run); nothing was changed")
         cap = compact_capacity(n_live, capacity)
         self._drop_bindings()
-        return self._compact_apply(ws, n_live, cap)
+        lv = getattr(self.loader, "version", None)
+        kept = self._compact_apply(ws, n_live, cap)
+        self._emb_moved(self.cfg.num_nodes, lv)
+        return kept
 
     @torch.no_grad()
     def stream_state(self) -> dict:
@@ -1203,11 +1227,150 @@ class TgnEngine:
         self.ctl.copy_(state["ctl"].to(self.dev, self.ctl.dtype))
         ld.cur_e_id = n
         ld.version = getattr(ld, "version", 0) + 1
+        self._emb_all = True
 
     # ------------------------------------------------------------------ read-only inference
     def embed_capacity(self) -> int:
         """Nodes per tgnx_tgn_embed call: the eval root capacity min(N, max_batch * (2 + max_neg))."""
         return int(_lib.lib().tgnx_tgn_embed_max_nodes(ctypes.byref(self.cfg)))
+
+    # ------------------------------------------------------------------ the embedding table (DESIGN §3b-9)
+    def enable_embedding_table(self) -> None:
+        """Keep a materialised [node_capacity, D] table of current eval-mode embeddings (off by default): queries with
+        cached=True read it instead of embedding their nodes again, and refresh_embeddings() recomputes only the rows
+        the batches since the last refresh made stale — their endpoints T and the nodes with a node of T in a valid
+        ring slot (two hops of that at layers = 2; include/tgnx.h has the rule).  Allocates the table and the stale
+        planes with every row stale.  While enabled, observe / eval batches pay one more launch (tgnx_embtab_touch).
+        One device only (ValueError at world > 1 / dp)."""
+        if self.world > 1 or self.dp:
+            raise ValueError("enable_embedding_table: one device only (world > 1 is not built)")
+        if self._emb_tab is None:
+            self._emb_alloc(max(self.node_capacity, int(self.cfg.num_nodes)))
+            self._emb_all = True
+
+    def disable_embedding_table(self) -> None:
+        """Free the table and the planes; every call issues exactly the launches it issues without the feature."""
+        self._emb_tab = self._emb_flags = self._emb_ids = self._emb_cnt = self._emb_ws = None
+
+    def _emb_alloc(self, cap: int) -> None:
+        nb = int(_lib.lib().tgnx_embtab_list_ws_bytes(cap))
+        if nb == 0:
+            raise RuntimeError(f"tgnx_embtab_list_ws_bytes: {cap} nodes are beyond the node id type")
+        self._emb_tab = torch.zeros(cap, self.cfg.mem_dim, dtype=torch.float32, device=self.dev)
+        self._emb_flags = torch.zeros(3 * cap, dtype=torch.uint8, device=self.dev)   # planes [3][N], N = cfg.num_nodes
+        self._emb_ids = torch.empty(cap, dtype=torch.long, device=self.dev)
+        self._emb_cnt = torch.zeros(1, dtype=torch.long, device=self.dev)
+        self._emb_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+
+    def _emb_touch(self, start: int, B: int) -> None:
+        """Mark the endpoints of event rows [start, start + B) stale (nothing to do while every row is)."""
+        if self._emb_tab is None or self._emb_all or B <= 0:
+            return
+        _lib.call("tgnx_embtab_touch", self._tab[0].data_ptr() + start * 8, self._tab[1].data_ptr() + start * 8, B,
+                  int(self.cfg.num_nodes), _p(self._emb_flags), self._stream())
+
+    def _emb_moved(self, n_old: int, loader_version) -> None:
+        """After a call that changed cfg.num_nodes, the row capacity or the loader's version without changing what an
+        old row embeds to (grow_nodes, reserve_nodes, compact_events): the table and the planes move to the new
+        capacity and plane stride, old rows keep their bits and their flags, new rows are stale (their embedding is
+        not zero: the skip path and the biases act on a zero memory row), and the table's record of the loader
+        version follows if it was current."""
+        ver = self._emb_ver
+        if ver is not None and ver[1] == loader_version:
+            self._emb_ver = (ver[0], getattr(self.loader, "version", None))
+        if self._emb_tab is None:
+            return
+        n, cap = int(self.cfg.num_nodes), max(self.node_capacity, int(self.cfg.num_nodes))
+        if n == n_old and cap <= self._emb_tab.shape[0]:
+            return
+        tab, flags = self._emb_tab, self._emb_flags
+        if cap > tab.shape[0]:
+            self._emb_alloc(cap)
+            self._emb_tab[:n_old].copy_(tab[:n_old])
+        if n != n_old or flags is not self._emb_flags:
+            # (D1 / D2 are zero between calls: only T carries flags across)
+            t_old = flags[:n_old].clone()
+            self._emb_flags.zero_()
+            self._emb_flags[:n_old].copy_(t_old)
+            self._emb_flags[n_old:n].fill_(1)
+
+    def invalidate_embeddings(self) -> None:
+        """Mark every row of the embedding table stale: for callers that write parameters, memory, last_update or the
+        ring directly (a raw tensor write the engine cannot see; model.load_state_dict / load_reference_state and the
+        loader's own calls are seen)."""
+        self._emb_all = True
+
+    @torch.no_grad()
+    def refresh_embeddings(self) -> torch.Tensor:
+        """Make the embedding table current and return the ids of the rows it recomputed (ascending int64, on the
+        device): tgnx_embtab_expand and tgnx_embtab_list turn the touched endpoints into the stale list, one host read
+        takes its length (as embed()'s validation reads the host), and tgnx_tgn_embed_into embeds the list in chunks
+        of embed_capacity() straight into the table.  Nothing stale: no embed launch, an empty tensor.  Everything
+        stale (after enable / invalidate_embeddings, a train step, flush, reset_state, a loaded stream state or
+        parameters, a replayed eval pass): the list is arange(N), without the list kernels or the host read.
+        The list is ascending and run-to-run identical, so a refresh is reproducible bit for bit; rows embedded in
+        one chunk share GEMM calls, so the bits of a row may differ from embed()'s of another node set within its
+        tolerance.  Read-only on the stream state as embed() is.  Nothing is flushed (see embed())."""
+        if self._emb_tab is None:
+            raise RuntimeError("refresh_embeddings: no embedding table (enable_embedding_table() first)")
+        self._settle()
+        N, cap = int(self.cfg.num_nodes), self.embed_capacity()
+        if cap <= 0:
+            raise RuntimeError(f"tgnx_tgn_embed_max_nodes: {_lib.lib().tgnx_last_error().decode()}")
+        ver = (getattr(self.model, "_param_version", None), getattr(self.loader, "version", None))
+        if ver != self._emb_ver:
+            self._emb_all, self._emb_ver = True, ver
+        b = self._buffers(0)
+        if self._emb_all:
+            self._emb_flags.zero_()
+            ids = torch.arange(N, device=self.dev)
+        else:
+            _lib.call("tgnx_embtab_expand", ctypes.byref(self.cfg), ctypes.byref(b), _p(self._emb_flags), self._stream())
+            _lib.call("tgnx_embtab_list", _p(self._emb_flags), N, int(self.cfg.layers), _p(self._emb_ids),
+                      _p(self._emb_cnt), _p(self._emb_ws), self._emb_ws.numel(), self._stream())
+            ids = self._emb_ids[:int(self._emb_cnt.item())].clone()
+        n = ids.numel()
+        self._emb_all = True    # (until the rows are written and checked)
+        for a in range(0, n, cap):
+            _lib.call("tgnx_tgn_embed_into", ctypes.byref(self.cfg), ctypes.byref(b), ids.data_ptr() + a * 8,
+                      min(cap, n - a), _p(self._emb_tab), self._stream())
+        if n:
+            self.check()
+        self._emb_all = False
+        return ids
+
+    def embedding_table(self) -> torch.Tensor:
+        """The [N, D] table of current embeddings, refreshed first (refresh_embeddings): row v is embed([v]) within its
+        tolerance — the export for a downstream index.  A view of the engine's table, not a copy: the next state
+        change (observe, an eval or train batch, flush, reset, a load, grow_nodes) invalidates it, and the next
+        refresh rewrites its stale rows in place; clone() what must outlive that."""
+        self.refresh_embeddings()
+        return self._emb_tab[:int(self.cfg.num_nodes)]
+
+    def _embed_lists(self, lists, cached: bool, what: str = "embed", full=None):
+        """One [n_i, D] block of embeddings per id list.  Uncached: one embed() over the concatenation, the blocks its
+        row ranges.  Cached: rows of the refreshed embedding table (index_select; the list `full`, which the caller
+        knows to be every node in order, is the table itself: no gather), ids checked against [0, N) by one host read
+        as embed() checks them."""
+        if not cached:
+            z = self.embed(torch.cat(lists))
+            out, a = [], 0
+            for x in lists:
+                out.append(z[a:a + x.numel()])
+                a += x.numel()
+            return out
+        if self._emb_tab is None:
+            raise RuntimeError(f"{what}: cached=True needs the embedding table (enable_embedding_table() first)")
+        N = int(self.cfg.num_nodes)
+        ids = torch.cat([x for i, x in enumerate(lists) if i != full])     # (never empty: `full` is not the sources)
+        if ids.numel() and bool(((ids < 0) | (ids >= N)).any()):
+            raise ValueError(f"{what}: node ids must be in [0, {N})")
+        tab = self.embedding_table()
+        return [tab if i == full else tab.index_select(0, x) for i, x in enumerate(lists)]
+
+    def _all_nodes(self, candidates) -> bool:
+        """The default candidates of an engine without dst_nodes: every node, in order."""
+        return candidates is None and self.dst_nodes is None
 
     @torch.no_grad()
     def embed(self, nodes, validate: bool = True) -> torch.Tensor:
@@ -1219,7 +1382,7 @@ class TgnEngine:
         again.  Nothing is flushed: after train steps call flush() first (as tgn_epoch.test does), or the stored
         messages of the last batches are not in the memory rows read here.  Node sets beyond embed_capacity() run in
         chunks.  validate: one host read checks the ids against [0, N) and raises ValueError; without it an id out
-        of range gets a zero row."""
+        of range gets a zero row.  embed_cached() reads the embedding table instead."""
         self._settle()
         nodes = torch.as_tensor(nodes).to(self.dev, torch.long).contiguous().view(-1)
         n, N = nodes.numel(), self.cfg.num_nodes
@@ -1237,6 +1400,13 @@ class TgnEngine:
         if n:
             self.check()
         return out
+
+    @torch.no_grad()
+    def embed_cached(self, nodes) -> torch.Tensor:
+        """embed() from the embedding table (enable_embedding_table; refreshed first, ids always validated): equal to
+        embed()'s rows within its tolerance, not bit for bit.  (embed(), recommend() and score() keep their
+        signatures; *_cached are their cached=True forms.)"""
+        return self._embed_lists([self._ids(nodes)], True)[0]
 
     def _ids(self, x) -> torch.Tensor:
         """Node ids (any integer sequence / tensor) as a flat contiguous int64 tensor on the device."""
@@ -1267,12 +1437,21 @@ class TgnEngine:
         dst_nodes when it has them, else every node).  Sources and candidates are embedded with embed() (read-only,
         chunked), then scored over all pairs and selected in one fused kernel with the model's link_pred parameters
         (ops.link_topk: ranked by logit, equal logits by the candidate's position in `candidates`).  k beyond the
-        candidate count pads with node id -1 and val 0."""
+        candidate count pads with node id -1 and val 0.  recommend_cached() reads the embedding table instead."""
+        return self._recommend(src, k, candidates, return_scores, False)
+
+    @torch.no_grad()
+    def recommend_cached(self, src, k: int, candidates=None, return_scores: bool = False):
+        """recommend() whose embeddings are rows of the embedding table (enable_embedding_table; refreshed first, so
+        only the rows stale since the last query are recomputed); when the candidates are every node in order the
+        table itself is the candidate operand, with no gather.  Also recommend_filtered(..., cached=True)."""
+        return self._recommend(src, k, candidates, return_scores, True)
+
+    def _recommend(self, src, k, candidates, return_scores, cached):
         from . import ops
         cand, src = self._candidates(candidates), self._ids(src)
-        z = self.embed(torch.cat([src, cand]))
-        out = ops.link_topk(z[:src.numel()], z[src.numel():], *self._link_weights(), k, sigmoid=True,
-                            return_scores=return_scores)
+        zs, zc = self._embed_lists([src, cand], cached, "recommend", 1 if self._all_nodes(candidates) else None)
+        out = ops.link_topk(zs, zc, *self._link_weights(), k, sigmoid=True, return_scores=return_scores)
         return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
 
     def _ragged_ids(self, x, n_src, what):
@@ -1320,7 +1499,8 @@ class TgnEngine:
 
     @torch.no_grad()
     def recommend_filtered(self, src, k: int, candidates=None, return_scores: bool = False, *,
-                           exclude_seen: bool = False, exclude_self: bool = False, exclude=None, per_source=None):
+                           exclude_seen: bool = False, exclude_self: bool = False, exclude=None, per_source=None,
+                           cached: bool = False):
         """recommend() with per-source exclusions and per-source candidate lists; read-only in the same way.
         exclude_seen: leave out the nodes in the source's neighbour-ring row (its most recent interaction partners).
         exclude_self: leave out the source itself.  exclude: more node ids per source, a (ptr, node_ids) tuple of
@@ -1330,7 +1510,8 @@ class TgnEngine:
         embeds src and the distinct listed nodes once and ranks each source over its list only
         (ops.link_topk(lists=...)): equal logits by the entry's place in the list; excluded entries are masked in a
         private copy.  Returns (val [Q, k], node_ids [Q, k][, logits [nnz]]), the logits aligned with the caller's
-        entries and NaN at an excluded one."""
+        entries and NaN at an excluded one.  cached: the embeddings are rows of the embedding
+        table (recommend_cached())."""
         from . import ops
         src = self._ids(src)
         Q, N = src.numel(), self.cfg.num_nodes
@@ -1343,7 +1524,7 @@ class TgnEngine:
                 raise ValueError("recommend: per_source and candidates are mutually exclusive")
             ptr, ids, longest = self._ragged_ids(per_source, Q, "recommend: per_source")
             uniq, pos = torch.unique(ids, return_inverse=True)
-            z = self.embed(torch.cat([src, uniq]))
+            zs, zu = self._embed_lists([src, uniq], cached, "recommend")
             seg = self._segments(ptr, ids.numel())
             pos = pos.clone()
             if exclude_self:
@@ -1352,14 +1533,14 @@ class TgnEngine:
                 comp = seg * (N + 1) + ids
                 at = torch.searchsorted(ex[2], comp).clamp(max=ex[2].numel() - 1)
                 pos[ex[2][at] == comp] = -1
-            out = ops.link_topk(z[:Q], z[Q:], *w, k, sigmoid=True, return_scores=return_scores, lists=(ptr, pos),
+            out = ops.link_topk(zs, zu, *w, k, sigmoid=True, return_scores=return_scores, lists=(ptr, pos),
                                 validate=False, max_len=longest)
             return (out[0], self._node_ids(out[1], uniq)) + tuple(out[3:])
         if ex is None and not exclude_self:
-            return self.recommend(src, k, candidates=candidates, return_scores=return_scores)
+            return self._recommend(src, k, candidates, return_scores, cached)
         cand = self._candidates(candidates)
-        z = self.embed(torch.cat([src, cand]))
-        out = ops.link_topk(z[:Q], z[Q:], *w, k, sigmoid=True, return_scores=return_scores, cand_key=cand,
+        zs, zc = self._embed_lists([src, cand], cached, "recommend", 1 if self._all_nodes(candidates) else None)
+        out = ops.link_topk(zs, zc, *w, k, sigmoid=True, return_scores=return_scores, cand_key=cand,
                             src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2],
                             validate=False)
         return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
@@ -1367,20 +1548,30 @@ class TgnEngine:
     @torch.no_grad()
     def score(self, src, dst) -> torch.Tensor:
         """The model's link probability [n] for the explicit pairs (src[i], dst[i]) at the current stream state:
-        embed() of both lists, then the LinkPredictor operator.  Read-only as embed() is."""
+        embed() of both lists, then the LinkPredictor operator.  Read-only as embed() is.  score_cached() reads the
+        embedding table instead."""
+        return self._score(src, dst, False)
+
+    @torch.no_grad()
+    def score_cached(self, src, dst) -> torch.Tensor:
+        """score() over rows of the embedding table (enable_embedding_table; refreshed first) instead of embed():
+        what cached=True is to the other queries (score()'s signature is fixed at (src, dst))."""
+        return self._score(src, dst, True)
+
+    def _score(self, src, dst, cached: bool) -> torch.Tensor:
         from . import ops
         src, dst = self._ids(src), self._ids(dst)
         if src.numel() != dst.numel():
             raise ValueError(f"score: {src.numel()} sources for {dst.numel()} destinations")
         n = src.numel()
-        z = self.embed(torch.cat([src, dst]))
+        zs, zd = self._embed_lists([src, dst], cached, "score")
         if n == 0:
-            return z.new_empty(0)
-        return ops.link_predictor(z[:n].contiguous(), z[n:].contiguous(), *self._link_weights(), sigmoid=True).view(-1)
+            return zs.new_empty(0)
+        return ops.link_predictor(zs.contiguous(), zd.contiguous(), *self._link_weights(), sigmoid=True).view(-1)
 
     @torch.no_grad()
     def rank(self, src, dst, candidates=None, return_scores: bool = False, *, exclude_seen: bool = False,
-             exclude_self: bool = False, exclude=None):
+             exclude_self: bool = False, exclude=None, cached: bool = False):
         """Where the model places the destination that happened: for every pair (src[i], dst[i]) the rank of dst[i]
         among the candidates recommend() would choose from (default: the same), at the current stream state and
         with recommend_filtered()'s exclusions (the "filtered" setting: the true destination itself is never
@@ -1389,7 +1580,8 @@ class TgnEngine:
         candidates scored above / equal to the destination, n compared, prob the destination's link probability.
         A destination outside `candidates` is ranked against all of them.  src, the candidates and dst are embedded
         once with embed(); the counts come from one fused pass (ops.link_rank), no [Q, C] logits unless asked for.
-        Read-only as recommend() is."""
+        Read-only as recommend() is.  cached: src and the candidate + destination rows are gathered from the embedding
+        table (enable_embedding_table; refreshed first)."""
         from . import ops
         src, dst = self._ids(src), self._ids(dst)
         Q, N = src.numel(), self.cfg.num_nodes
@@ -1400,24 +1592,29 @@ class TgnEngine:
         cand = self._candidates(candidates)
         C = cand.numel()
         ex = self._exclusions(src, exclude_seen, exclude)
-        z = self.embed(torch.cat([src, cand, dst]))
+        if cached:
+            zs, zc = self._embed_lists([src, torch.cat([cand, dst])], True, "rank")
+        else:
+            z = self.embed(torch.cat([src, cand, dst]))
+            zs, zc = z[:Q], z[Q:]
         w = self._link_weights()
         rank, gt, eq, n, tlogit = ops.link_rank(
-            z[:Q], z[Q:], *w, C + torch.arange(Q, device=self.dev), n_count=C, cand_key=torch.cat([cand, dst]),
+            zs, zc, *w, C + torch.arange(Q, device=self.dev), n_count=C, cand_key=torch.cat([cand, dst]),
             src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2], validate=False)
         out = (rank, gt, eq, n, torch.sigmoid(tlogit))
         if return_scores:  # (over the same C + Q rows: the operands, and so the bits, of the counted logits)
-            out += (ops.link_topk(z[:Q], z[Q:], *w, 1, sigmoid=False, return_scores=True)[2][:, :C].contiguous(),)
+            out += (ops.link_topk(zs, zc, *w, 1, sigmoid=False, return_scores=True)[2][:, :C].contiguous(),)
         return out
 
     def rank_events(self, start: int, B: int, candidates=None, *, exclude_seen: bool = False,
-                    exclude_self: bool = False, exclude=None):
+                    exclude_self: bool = False, exclude=None, cached: bool = False):
         """One prequential step over resident rows [start, start + B): rank() of src[e] -> dst[e] at the state before
-        them, then observe(start, B).  Returns rank()'s tuple."""
+        them, then observe(start, B).  Returns rank()'s tuple.  cached: rank(cached=True) — each step then embeds only
+        the rows the previous step's batch made stale."""
         start, B = int(start), int(B)
         check_observe_args(start, B, self.cfg.max_batch, self.num_events, self.world)
         out = self.rank(self._tab[0][start:start + B], self._tab[1][start:start + B], candidates,
-                        exclude_seen=exclude_seen, exclude_self=exclude_self, exclude=exclude)
+                        exclude_seen=exclude_seen, exclude_self=exclude_self, exclude=exclude, cached=cached)
         self.observe(start, B)
         return out
 
@@ -1457,12 +1654,14 @@ class TgnEngine:
         """Rewind the eval cursor to split_lo (the start of a pass).  Like every non-train call it settles a deferred
         data-parallel apply and makes the next train step prepare its batch again."""
         self._settle()
+        self._emb_all = True
         self.ctl[18] = 0
 
     def _eval_step(self):
         if self._ev is None:
             raise RuntimeError("TgnEngine: no eval pass bound (bind_eval_resident)")
         lo, hi, batch, Kn = self._ev
+        self._emb_all = True   # (the batch comes from the device cursor: the host does not see its rows)
         _lib.call("tgnx_tgn_eval_step_resident", ctypes.byref(self.cfg), self._ev_buf_ref, lo, hi, batch, Kn, self.dp_rank,
                   self.world, self.seed, ctypes.c_void_p(self._ev_rr.data_ptr()), self._stream())
 
@@ -1500,6 +1699,7 @@ class TgnEngine:
             raise RuntimeError("TgnEngine: no captured eval step (capture_eval after bind_eval_resident; a new binding or "
                                "a grown workspace drops it)")
         self._settle()
+        self._emb_all = True
         g1, k, gk = self._ev_graphs
         done = 0
         while done < n:
@@ -1586,6 +1786,7 @@ class TgnEngine:
         return self.dp and self._pp()
 
     def _pre(self, prefetched: bool = False, parity=None, apply=None):
+        self._emb_all = True
         adv, fb = self._f[:2]
         lo, hi, batch = self._res
         st = self._stream()
@@ -1683,6 +1884,7 @@ class TgnEngine:
         if not self._apply_pending:
             return
         self._apply_pending = False  # (cleared whether or not the apply succeeds: a failed one is not retried)
+        self._emb_all = True
         _lib.call("tgnx_tgn_apply_rows_update", self._cfg_ref, self._buf_ref, ctypes.c_void_p(self.xgather.data_ptr()),
                   ctypes.c_int64(self.xgather.shape[0]), self._stream())
 
@@ -1746,6 +1948,7 @@ class TgnEngine:
         """n resident steps: whole captured k-step groups wherever the set parity and the prefetch allow, single
         replays (or the priming eager step) otherwise.  The same steps as n calls of replay_resident()."""
         grp = getattr(self, "_group", None)
+        self._emb_all = True
         done = 0
         while done < n:
             if grp and n - done >= grp[0] and self._parity == 0 and self._prefetch_valid():
@@ -1757,6 +1960,7 @@ class TgnEngine:
                 done += 1
 
     def replay_resident(self):
+        self._emb_all = True
         g1, g2, gs = self._graphs
         if self._pipelined() and not self._prefetch_valid():
             self.resident_train_step()   # marks + scans this batch first (eager), prefetches the next

@@ -20,6 +20,8 @@ updates the stores, the memory and the ring in eval order.
       the trained model ranks highest for each source at the current stream state (TgnEngine.recommend; read-only)
   recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclude_seen, exclude_self, exclude,
       per_source): the same with per-source exclusions or per-source candidate lists (TgnEngine.recommend_filtered)
+  embedding_table(model, neighbor_loader) -> [N, D]: the current embeddings of every node, kept incrementally
+      (TgnEngine.embedding_table); recommend_filtered / rank_stream take cached=True to read it
   observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
       table and taken into memory, stores and ring as test() batches would leave them, without negatives or scores
       (TgnEngine.observe_events)
@@ -190,7 +192,8 @@ def recommend(model, neighbor_loader, src, k, candidates=None):
     """Top-k link recommendation with the engine train() / test() attached to the model: for every node of `src` the
     k candidates (default: the engine's destination set) with the highest LinkPredictor output at the current stream
     state, as (val [Q, k], node_ids [Q, k]).  Read-only (TgnEngine.recommend).  Straight after train() the memory is
-    switched to eval first, exactly as test() does (TGNMemory.train(False), memory_module.py:209-215)."""
+    switched to eval first, exactly as test() does (TGNMemory.train(False), memory_module.py:209-215).
+    recommend_filtered(..., cached=True) is the form that reads the engine's embedding table."""
     eng = getattr(_owner(model), "_tgnx_engine", None)
     if eng is None or eng.loader is not neighbor_loader:
         raise RuntimeError("tgnx recommend: no engine bound to this model / neighbor_loader yet (run train() or test() "
@@ -203,10 +206,12 @@ def recommend(model, neighbor_loader, src, k, candidates=None):
 
 @torch.no_grad()
 def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclude_seen=False, exclude_self=False,
-                       exclude=None, per_source=None):
+                       exclude=None, per_source=None, cached=False):
     """recommend() with per-source exclusions (exclude_seen: the source's recent interaction partners; exclude_self;
     exclude: more node ids per source) or a candidate list per source (per_source), TgnEngine.recommend_filtered's
-    keywords passed through.  Read-only; switches the memory to eval first as recommend() does."""
+    keywords passed through.  cached: read the engine's embedding table (enabled here if it is not) instead of
+    embedding the sources and candidates again; without exclusions this is recommend() from the table.  Read-only;
+    switches the memory to eval first as recommend() does."""
     eng = getattr(_owner(model), "_tgnx_engine", None)
     if eng is None or eng.loader is not neighbor_loader:
         raise RuntimeError("tgnx recommend_filtered: no engine bound to this model / neighbor_loader yet (run train() "
@@ -214,19 +219,24 @@ def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclu
     if eng._mode_train:
         eng.flush()
         eng._mode_train = False
+    if cached:
+        eng.enable_embedding_table()
     return eng.recommend_filtered(src, k, candidates=candidates, exclude_seen=exclude_seen, exclude_self=exclude_self,
-                                  exclude=exclude, per_source=per_source)
+                                  exclude=exclude, per_source=per_source, cached=cached)
 
 
 @torch.no_grad()
 def rank_stream(model, neighbor_loader, lo, hi, batch, candidates=None, ks=(1, 10, 50), *, exclude_seen=False,
-                exclude_self=False):
+                exclude_self=False, cached=False):
     """Prequential full-catalogue ranking over rows [lo, hi) of the event table of the engine train() / test()
     attached to the model: every batch of `batch` events is ranked at the state before it (TgnEngine.rank_events: the
     true destination against every candidate recommend() would choose from, recommend_filtered()'s exclusions), then
     observed.  Returns {"mrr": mean 1 / rank, "hits@k": mean rank <= k for k in ks, "rank": float64 [hi - lo] on the
     device}; skipped events (NaN rank) count as misses.  The means are taken on the device: one synchronisation, at the
-    end.  Switches the memory to eval first as recommend() does."""
+    end.  Switches the memory to eval first as recommend() does.  cached: rank from the engine's embedding table
+    (enabled here if it is not), so that each batch embeds only the rows the batch before it made stale instead of
+    every candidate; ranks may differ from the uncached ones where two competing logits are closer than the
+    embeddings' tolerance."""
     eng = _bound_engine(model, neighbor_loader, "rank_stream")
     lo, hi, batch = int(lo), int(hi), int(batch)
     if not (0 <= lo <= hi <= eng.num_events) or not (0 < batch <= eng.cfg.max_batch):
@@ -235,14 +245,30 @@ def rank_stream(model, neighbor_loader, lo, hi, batch, candidates=None, ks=(1, 1
     if eng._mode_train:
         eng.flush()
         eng._mode_train = False
+    if cached:
+        eng.enable_embedding_table()
     ranks = [eng.rank_events(a, min(batch, hi - a), candidates, exclude_seen=exclude_seen,
-                             exclude_self=exclude_self)[0] for a in range(lo, hi, batch)]
+                             exclude_self=exclude_self, cached=cached)[0] for a in range(lo, hi, batch)]
     rank = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.float64, device=eng.dev)
     stats = torch.stack([torch.nan_to_num(1.0 / rank, nan=0.0).sum()] + [(rank <= k).sum().double() for k in ks])
     stats = (stats / max(hi - lo, 1)).tolist()
     out = {"mrr": stats[0], "rank": rank}
     out.update({f"hits@{k}": v for k, v in zip(ks, stats[1:])})
     return out
+
+
+@torch.no_grad()
+def embedding_table(model, neighbor_loader):
+    """The [N, D] table of current eval-mode embeddings of the engine train() / test() attached to the model
+    (TgnEngine.embedding_table; the table is enabled here if it is not, and only its stale rows are recomputed): the
+    export for a downstream index.  A view that the next state change invalidates: clone() what must outlive it.
+    Switches the memory to eval first as recommend() does."""
+    eng = _bound_engine(model, neighbor_loader, "embedding_table")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    eng.enable_embedding_table()
+    return eng.embedding_table()
 
 
 @torch.no_grad()
