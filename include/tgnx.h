@@ -803,6 +803,33 @@ int tgnx_link_predictor_rank(int64_t n_src, int64_t n_cand, int64_t d_in, int64_
                              int64_t* out_eq /* [n_src] */, int64_t* out_n /* [n_src] */,
                              float* out_tlogit /* [n_src] */, void* ws, size_t ws_bytes, void* stream);
 
+/* Embedding-space nearest neighbours with the selection fused in (csrc/tgnx_knn.hip): for every query
+ * row q the k candidate rows with the largest similarity, without a [n_q, n_cand] score matrix.  z_q [n_q, D] and
+ * z_cand [n_cand, D] row-major with pitch D (any alignment), 1 <= D <= 256, 1 <= k <= TGNX_TOPK_MAX.
+ * score[q][c] = z_q[q] · z_cand[c] (TGNX_KNN_DOT), or the dot product of the two rows each scaled by 1 / sqrt(Σ z²)
+ * (TGNX_KNN_COSINE; a row whose sum of squares is 0 scales by 0: its scores are 0, not NaN).
+ * Selection, padding and exclusions as tgnx_link_predictor_topk_filtered: larger score first, equal scores (float ==)
+ * by lower candidate position, a NaN score never selected, slots past the candidates left idx -1 / val -INFINITY;
+ * cand_key [n_cand], q_key [n_q] (candidate c is out for query q when its key equals q_key[q]: "not myself"),
+ * excl_ptr [n_q + 1] / excl_key [nnz] with ascending segments, all optional (NULL); excl_ptr is clamped into
+ * [0, nnz], a decreasing pair reads as an empty segment, and no content of the arrays causes an access outside their
+ * stated sizes.  out_all (optional, [n_q, n_cand]): the UNMASKED scores exactly as the selection compared them.
+ * n_q = 0 does nothing; n_cand = 0 fills the padding.
+ * A score is one f32 accumulator's fma chain (v_mfma_f32_16x16x4_f32) from 0 over a fixed permutation of k, the same
+ * for every pair (csrc/tgnx_knn.hip states it), and a row norm one fixed order per row: a pair's bits depend on its
+ * two rows, D and the metric only, not on n_q, n_cand, the rows' positions or the grid.  No atomics, no allocation,
+ * no host synchronisation: graph-capturable, run-to-run identical.
+ * ws: tgnx_embed_knn_ws_bytes bytes, 16-byte aligned (the prepared rows, the per-chunk partial lists; monotone in
+ * n_cand). */
+#define TGNX_KNN_DOT 0
+#define TGNX_KNN_COSINE 1
+size_t tgnx_embed_knn_ws_bytes(int64_t n_q, int64_t n_cand, int64_t D, int32_t k);
+int tgnx_embed_knn(int64_t n_q, int64_t n_cand, int64_t D, const float* z_q, const float* z_cand, int32_t metric,
+                   int32_t k, const int64_t* cand_key /* optional [n_cand] */, const int64_t* q_key /* optional [n_q] */,
+                   const int64_t* excl_ptr /* optional [n_q + 1] */, const int64_t* excl_key /* [nnz] */, int64_t nnz,
+                   float* out_val /* [n_q, k] */, int64_t* out_idx /* [n_q, k] */,
+                   float* out_all /* optional [n_q, n_cand] */, void* ws, size_t ws_bytes, void* stream);
+
 /* TransformerConv's attention (modules/emb_module.py:21-29; PyG TransformerConv, concat, no beta): for
  * destination i with incoming edges p in [indptr[i], indptr[i+1]) (rows of the per-edge k, v, e [E, H*C];
  * q [n_dst, H*C]), per head h: a_p = q_i·(k_p + e_p) / sqrt(C), α = softmax over i's edges (max subtracted,

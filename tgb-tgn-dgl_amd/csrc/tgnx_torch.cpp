@@ -430,6 +430,34 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> predictor_topk_filtered(
   return {val, idx, all};
 }
 
+// nearest neighbours in embedding space with the top-k selection fused in (tgnx_embed_knn, csrc/tgnx_knn.hip):
+// (val [Q, k], idx [Q, k] positions into z_cand, scores [Q, C] unmasked or an empty tensor)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> embed_knn(const at::Tensor& z_q, const at::Tensor& z_cand, int64_t metric,
+                                                         int64_t k, bool return_scores,
+                                                         const c10::optional<at::Tensor>& cand_key,
+                                                         const c10::optional<at::Tensor>& q_key,
+                                                         const c10::optional<at::Tensor>& excl_ptr,
+                                                         const c10::optional<at::Tensor>& excl_key) {
+  dev_tensor(z_q, at::kFloat, "z_q");
+  dev_tensor(z_cand, at::kFloat, "z_cand");
+  TORCH_CHECK(z_q.dim() == 2 && z_cand.dim() == 2 && z_q.size(1) == z_cand.size(1), "z_q [Q, D] and z_cand [C, D]");
+  TORCH_CHECK(k >= 1 && k <= TGNX_TOPK_MAX, "k must be in [1, ", TGNX_TOPK_MAX, "], got ", k);
+  TORCH_CHECK(metric == TGNX_KNN_DOT || metric == TGNX_KNN_COSINE, "metric must be 0 (dot) or 1 (cosine), got ", metric);
+  same_device(z_q, {&z_cand});
+  const int64_t Q = z_q.size(0), C = z_cand.size(0), D = z_q.size(1);
+  const KeyArgs f = key_args(z_q, C, cand_key, q_key, excl_ptr, excl_key);
+  const c10::OptionalDeviceGuard guard(z_q.device());
+  auto [val, idx, all] = topk_outputs(z_q, C, k, return_scores);
+  const size_t nb = tgnx_embed_knn_ws_bytes(Q, C, D, (int32_t)k);
+  at::Tensor ws = at::empty({(int64_t)nb}, z_q.options().dtype(at::kByte));
+  check_rc(tgnx_embed_knn(Q, C, D, z_q.data_ptr<float>(), z_cand.data_ptr<float>(), (int32_t)metric, (int32_t)k,
+                          f.cand_key, f.src_key, f.excl_ptr, f.excl_key, f.nnz, val.data_ptr<float>(),
+                          idx.data_ptr<int64_t>(), return_scores ? all.data_ptr<float>() : nullptr, ws.data_ptr(), nb,
+                          cur_stream()),
+           "tgnx_embed_knn");
+  return {val, idx, all};
+}
+
 // LinkPredictor + top-k over a candidate list per source (tgnx_link_predictor_topk_lists):
 // (val [B, k], idx [B, k], slot [B, k], logits [nnz] or empty, n_invalid [1])
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_topk_lists(
@@ -958,6 +986,9 @@ TORCH_LIBRARY(tgnx, m) {
         "Tensor? b_dst, Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores, Tensor? cand_key, "
         "Tensor? src_key, Tensor? excl_ptr, Tensor? excl_key) -> (Tensor, Tensor, Tensor)",
         &predictor_topk_filtered);
+  m.def("embed_knn(Tensor z_q, Tensor z_cand, int metric, int k, bool return_scores, Tensor? cand_key, Tensor? q_key, "
+        "Tensor? excl_ptr, Tensor? excl_key) -> (Tensor, Tensor, Tensor)",
+        &embed_knn);
   m.def("predictor_topk_lists(Tensor z_src, Tensor z_cand, Tensor w_src, Tensor? b_src, Tensor w_dst, Tensor? b_dst, "
         "Tensor w_out, Tensor b_out, int k, bool sigmoid, bool return_scores, Tensor list_ptr, Tensor list_idx, "
         "int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",

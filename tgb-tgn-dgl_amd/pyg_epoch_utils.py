@@ -5,3 +5,4 @@ from tgnx.tgn_epoch import recommend_filtered  # noqa: F401
 from tgnx.tgn_epoch import rank_stream  # noqa: F401
 from tgnx.tgn_epoch import grow_nodes, observe_grow  # noqa: F401
 from tgnx.tgn_epoch import embedding_table  # noqa: F401
+from tgnx.tgn_epoch import similar  # noqa: F401

@@ -101,6 +101,9 @@ SIGNATURES = {
     "tgnx_link_predictor_rank_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "tgnx_link_predictor_rank": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, c_i64, P, P, P, P, P,
                                                 c_i64, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_embed_knn_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i32]),
+    "tgnx_embed_knn": (ctypes.c_int, [c_i64, c_i64, c_i64, P, P, c_i32, c_i32, P, P, P, P, c_i64, P, P, P, P, c_sz,
+                                      c_vp]),
     "tgnx_edge_attn_fwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, c_vp]),
     "tgnx_edge_attn_bwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, P, P, P, P, c_vp]),
     # per-operator backward (tgnx_ops_bwd.hip)

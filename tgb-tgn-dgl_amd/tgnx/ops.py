@@ -10,7 +10,8 @@ tcsr_sample (TGL t-CSR, utils.py:73), gemm_f32 (MFMA fp32 GEMM), and the TGN mod
 gru_update (TGNMemory's GRUCell / RNNCell, memory_module.py:70-78), predictor (LinkPredictor decoder.py:12-27;
 EdgePredictor model_utils.py:165-195), predictor_topk (LinkPredictor over all pairs with the top-k selection fused
 in, csrc/tgnx_topk.hip; `link_topk` below; predictor_topk_filtered / predictor_topk_lists: the same with per-source
-exclusions by key / a candidate list per source) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
+exclusions by key / a candidate list per source), embed_knn (nearest neighbours in embedding space, dot or cosine, on the
+f32 MFMA with the same selection and exclusions, csrc/tgnx_knn.hip; `embed_knn` below) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
 emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function), time_encode (TimeEncoder)
 and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
 gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd, msg_agg_mean_bwd) sit
@@ -30,7 +31,7 @@ import torch
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "predictor_topk", "edge_attn_fwd", "edge_attn_bwd",
-       "predictor_topk_filtered", "predictor_topk_lists", "predictor_rank",
+       "predictor_topk_filtered", "predictor_topk_lists", "predictor_rank", "embed_knn",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
@@ -259,6 +260,51 @@ def link_rank(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, target, n
         z_cand.size(0) if n_count is None else int(n_count), key(cand_key), key(src_key), ptr, keys)
     rank = torch.add(gt, eq.double(), alpha=0.5).add_(1.0)
     return rank.masked_fill_(torch.isnan(tlogit), float("nan")), gt, eq, n, tlogit
+
+
+KNN_METRICS = {"dot": 0, "cosine": 1}     # TGNX_KNN_DOT / TGNX_KNN_COSINE
+TOPK_MAX = 128                            # TGNX_TOPK_MAX
+
+
+def knn_metric(metric) -> int:
+    """The C ABI's metric code of a metric name; ValueError for an unknown one."""
+    if metric not in KNN_METRICS:
+        raise ValueError(f"embed_knn: metric must be one of {sorted(KNN_METRICS)}, got {metric!r}")
+    return KNN_METRICS[metric]
+
+
+def knn_k(k) -> int:
+    """k as an int inside the selection's range [1, TGNX_TOPK_MAX]; ValueError otherwise."""
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"embed_knn: k must be in [1, {TOPK_MAX}], got {k}")
+    return k
+
+
+@torch.no_grad()
+def embed_knn(z_q, z_cand, k, metric="cosine", return_scores=False, cand_key=None, q_key=None, exclude=None,
+              validate=True):
+    """The k nearest candidate rows of every query row in embedding space (tgnx_embed_knn): z_q [n_q, D], z_cand
+    [n_cand, D], D <= 256; metric "cosine" (rows scaled by 1 / sqrt(sum z^2); a zero row scores 0) or "dot".  All
+    n_q x n_cand scores come from the f32 MFMA and are selected in the same kernel: no [n_q, n_cand] matrix handed to
+    torch.topk.  Returns (val [n_q, k], idx [n_q, k]) and, with return_scores, the unmasked scores [n_q, n_cand] the
+    selection compared.  idx holds positions into z_cand, ordered by larger score, equal scores by lower position; a
+    NaN score is never selected; slots past the candidates hold idx -1 and val -inf.  A pair's score has the same
+    bits whatever the other rows, their order and their number are.  Inference only: no autograd.
+
+    Exclusions as link_topk's filtered form: a candidate's key is cand_key[c] (int64 [n_cand]; default its position);
+    it is left out for query q when the key equals q_key[q] (int64 [n_q]: "not myself") or occurs in q's segment of
+    exclude = (ptr [n_q + 1], keys), each segment ascending.  validate: one host read checks exclude's shape and
+    order (ValueError); without it the kernel still keeps every access inside the arrays."""
+    code, k = knn_metric(metric), knn_k(k)
+    dev, n_q = z_q.device, z_q.size(0)
+    key = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.long).contiguous().view(-1)  # noqa: E731
+    ptr = keys = None
+    if exclude is not None:
+        ptr, keys, _ = _ragged(exclude, n_q, dev, "exclude", validate, need_sorted=True)
+    val, idx, scores = load().embed_knn(z_q.detach().contiguous(), z_cand.detach().contiguous(), code, k,
+                                        bool(return_scores), key(cand_key), key(q_key), ptr, keys)
+    return (val, idx, scores) if return_scores else (val, idx)
 
 
 class _TimeEncode(torch.autograd.Function):

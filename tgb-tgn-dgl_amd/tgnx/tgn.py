@@ -1618,6 +1618,37 @@ class TgnEngine:
         self.observe(start, B)
         return out
 
+    @torch.no_grad()
+    def similar(self, nodes, k: int, candidates=None, *, metric: str = "cosine", exclude_self: bool = True,
+                exclude_seen: bool = False, exclude=None, cached: bool = False, return_scores: bool = False):
+        """Which nodes are like these: for every node of `nodes` its k nearest neighbours in embedding space at the
+        current stream state, (score [Q, k], node_ids [Q, k][, scores [Q, C] unmasked]).  metric: "cosine" (default;
+        a node with a zero embedding scores 0) or "dot".  candidates: node ids (default: every node [0, N) in order,
+        whatever dst_nodes is — similarity is not restricted to destinations).  The link predictor takes no part:
+        queries and candidates are embedded with embed() (read-only, chunked), then all pairs are scored on the f32
+        MFMA and selected in the same kernel (ops.embed_knn: larger score first, equal scores by the candidate's
+        position in `candidates`).  exclude_self (default True: under cosine a node is its own nearest neighbour)
+        leaves the query node out, exclude_seen the nodes in its neighbour-ring row, exclude more node ids per query
+        (recommend_filtered()'s forms); exclusion is by node id, so every position of a duplicated candidate goes.
+        k beyond the candidates left pads with node id -1 and score -inf.  cached: the embeddings are rows of the
+        embedding table (enable_embedding_table; refreshed first), and with the default candidates the table itself
+        is the candidate operand, with no gather.  Read-only as recommend() is.  One device only."""
+        from . import ops
+        if self.world > 1:
+            raise ValueError("similar: one device only (world > 1 is not built)")
+        ops.knn_metric(metric)
+        k = ops.knn_k(k)
+        nodes = self._ids(nodes)
+        every = candidates is None
+        cand = torch.arange(int(self.cfg.num_nodes), device=self.dev) if every else self._ids(candidates)
+        # (embed() / the table path check every id against [0, N) with one host read, before the ring rows are read)
+        zq, zc = self._embed_lists([nodes, cand], cached, "similar", 1 if every else None)
+        ex = self._exclusions(nodes, exclude_seen, exclude)
+        out = ops.embed_knn(zq, zc, k, metric=metric, return_scores=return_scores, cand_key=None if every else cand,
+                            q_key=nodes if exclude_self else None, exclude=None if ex is None else ex[:2],
+                            validate=False)
+        return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
+
     # ------------------------------------------------------------------ resident eval pass
     def bind_eval_resident(self, split_lo: int, split_hi: int, batch: int, negs):
         """A validation / test pass over events [split_lo, split_hi) in batches of `batch`, resident on the device:

@@ -20,6 +20,8 @@ updates the stores, the memory and the ring in eval order.
       the trained model ranks highest for each source at the current stream state (TgnEngine.recommend; read-only)
   recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclude_seen, exclude_self, exclude,
       per_source): the same with per-source exclusions or per-source candidate lists (TgnEngine.recommend_filtered)
+  similar(model, neighbor_loader, nodes, k, candidates=None, *, metric, exclude_self, exclude_seen, exclude, cached)
+      -> (score [Q, k], node_ids [Q, k]): every node's k nearest neighbours in embedding space (TgnEngine.similar)
   embedding_table(model, neighbor_loader) -> [N, D]: the current embeddings of every node, kept incrementally
       (TgnEngine.embedding_table); recommend_filtered / rank_stream take cached=True to read it
   observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
@@ -223,6 +225,24 @@ def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclu
         eng.enable_embedding_table()
     return eng.recommend_filtered(src, k, candidates=candidates, exclude_seen=exclude_seen, exclude_self=exclude_self,
                                   exclude=exclude, per_source=per_source, cached=cached)
+
+
+@torch.no_grad()
+def similar(model, neighbor_loader, nodes, k, candidates=None, *, metric="cosine", exclude_self=True, exclude_seen=False,
+            exclude=None, cached=False):
+    """Nearest neighbours in embedding space with the engine train() / test() attached to the model: for every node of
+    `nodes` the k candidates (default: every node) most similar to it at the current stream state, as (score [Q, k],
+    node_ids [Q, k]); TgnEngine.similar's keywords passed through (metric "cosine" / "dot"; exclude_self, on by
+    default; exclude_seen; exclude).  cached: read the engine's embedding table (enabled here if it is not).
+    Read-only; switches the memory to eval first as recommend() does."""
+    eng = _bound_engine(model, neighbor_loader, "similar")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    if cached:
+        eng.enable_embedding_table()
+    return eng.similar(nodes, k, candidates=candidates, metric=metric, exclude_self=exclude_self,
+                       exclude_seen=exclude_seen, exclude=exclude, cached=cached)
 
 
 @torch.no_grad()
