@@ -664,6 +664,46 @@ int tgnx_tgn_grow_nodes(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf,
 int tgnx_tgn_grow_store(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t n_new, int64_t* new_store,
                         int64_t* bad, void* stream);
 
+/* Forgetting nodes (csrc/tgnx_forget.hip): erase a node set F from the stream state in place.  With
+ * N = cfg->num_nodes, K = cfg->ring <= 32 and num_events the table's valid rows (cfg->num_events is the capacity):
+ *   own rows, v in F    memory[v] = 0, last_update[v] = 0, node_gen[v] = 0, the store's node words {0, 0, 0, 0}, the
+ *                       ring row nbr = -1, e_id = -1, t = -1.0f in every slot: what tgnx_tgn_grow_nodes leaves for a
+ *                       new row;
+ *   ring rows, u not in F   a slot is valid when e_id >= 0 and nbr != -1.  Valid slots whose nbr is in F are removed;
+ *                       the surviving (e_id, nbr) pairs keep their order at the front of the row, every other slot
+ *                       becomes (-1, -1); the t column becomes ev_t[e_id] of the survivors ranked descending, ties by
+ *                       slot (as the ring insert ranks t apart from e_id), -1.0f behind them.  A row that loses
+ *                       nothing is not written;
+ *   store runs, u not in F  an entry e of the s run is dropped when ev_dst[e] is in F, of the d run when ev_src[e] is;
+ *                       the survivors are packed in order at the front of the same run (off unchanged, cnt reduced; an
+ *                       emptied run becomes {0, 0}).  Arena words behind a shortened run keep their old values;
+ *   nothing else is written (ctl, parameters, the event table: the rows only F kept alive are dead until a compaction).
+ * Two calls with one host read between them.  ws is tgnx_tgn_forget_ws_bytes(cfg) bytes, 16-B aligned, not zeroed,
+ * and must pass unchanged from plan to apply: [8 int64 record | N-bit bitmap of F | one byte per node].  The record:
+ * [0] distinct nodes of F, [1] ring slots to remove, [2] ring rows that lose a slot, [3] store entries to drop (rows
+ * and runs of F itself are not counted), [4] bad ids, [5] N, [6] num_events.
+ * tgnx_tgn_forget_plan (3 launches; 2 for n = 0) writes only ws.  Duplicate ids are allowed.  Counted into record[4]
+ * and never used as an index: an id outside [0, N); a valid ring slot whose nbr is outside [0, N) or whose e_id is
+ * >= num_events; a run {off, cnt} with cnt < 0 or outside the arena words [0, 2 * num_events); an arena entry outside
+ * [0, num_events) or the other endpoint of its event outside [0, N).  All sums are integer: the record is
+ * deterministic.
+ * tgnx_tgn_forget_apply (2 launches) rewrites the state as above; both kernels check the record first and store
+ * nothing unless it is a clean plan for this N and num_events (the caller reads the record after the plan and does
+ * not call apply otherwise).  emb_flags (NULL: none) is plane T of the embedding table's flags: 1 is stored for every
+ * v in F and every ring row that is rewritten (idempotent plain stores, as tgnx_embtab_touch).
+ * tgnx_ring_forget is the ring part alone, plan and apply in one call (4 launches), for a loader without an engine:
+ * with ev_t NULL the t column drops the slots e_id drops (equal to the rule above on a time-ordered stream) and
+ * num_events is ignored.  The caller reads the record afterwards: with record[4] != 0 nothing was stored.
+ * Null or mis-sized arguments, K > 32: TGNX_EINVAL, nothing launched; 2^31 nodes or more: TGNX_ETOOBIG.  One device
+ * only.  Test: tests/test_gpu_tgn_forget.py. */
+size_t tgnx_tgn_forget_ws_bytes(const tgnx_tgn_config* cfg);
+int tgnx_tgn_forget_plan(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t num_events,
+                         const int64_t* ids, int64_t n, void* ws, size_t ws_bytes, void* stream);
+int tgnx_tgn_forget_apply(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t num_events, const void* ws,
+                          size_t ws_bytes, uint8_t* emb_flags, void* stream);
+int tgnx_ring_forget(int64_t* nbr, int64_t* eid, float* rt, const float* ev_t, int64_t num_events, int64_t N,
+                     int32_t K, const int64_t* ids, int64_t n, void* ws, size_t ws_bytes, void* stream);
+
 /* train(False): update the memory of every node from its stored messages, clear the stores
  * (memory_module.py:209-215).  Every row is computed from the pre-flush state (:212 updates arange(N) at
  * once).  Graphs with more nodes than the workspace's GRU row capacity run in chunks that read a snapshot

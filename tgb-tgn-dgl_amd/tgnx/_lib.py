@@ -72,6 +72,10 @@ SIGNATURES = {
     "tgnx_tgn_compact_apply": (ctypes.c_int, [P, P, c_i64, c_i64, P, P, P, P, P, P, c_i64, P, c_sz, c_vp]),
     "tgnx_tgn_grow_nodes": (ctypes.c_int, [P, P, c_i64, c_i64, P, P, c_vp]),
     "tgnx_tgn_grow_store": (ctypes.c_int, [P, P, c_i64, P, P, c_vp]),
+    "tgnx_tgn_forget_ws_bytes": (c_sz, [P]),
+    "tgnx_tgn_forget_plan": (ctypes.c_int, [P, P, c_i64, P, c_i64, P, c_sz, c_vp]),
+    "tgnx_tgn_forget_apply": (ctypes.c_int, [P, P, c_i64, P, c_sz, P, c_vp]),
+    "tgnx_ring_forget": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, c_i32, P, c_i64, P, c_sz, c_vp]),
     "tgnx_tgn_flush": (ctypes.c_int, [P, P, P, ctypes.c_size_t, c_vp]),
     "tgnx_tgn_flush_scratch_bytes": (ctypes.c_size_t, [P]),
     "tgnx_tgn_apply_rows": (ctypes.c_int, [P, P, P, c_i64, c_vp]),

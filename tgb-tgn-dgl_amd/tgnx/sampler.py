@@ -7,6 +7,8 @@ Same constructor, attributes (`neighbors`, `e_id`, `t`, `_assoc`, `size`,
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -76,6 +78,38 @@ class LastNeighborLoader:
             alloc = (new["nbr"], new["eid"], new["rt"], new["assoc"])
         self._install(*alloc, n)
         return n
+
+    @torch.no_grad()
+    def forget(self, ids) -> dict:
+        """Erase the nodes `ids` (duplicates allowed) from the ring of a loader used alone (tgnx_ring_forget): their
+        own rows become what reset_state leaves (neighbors -1, e_id -1, t -1.0) and every valid slot (e_id >= 0 and
+        neighbors != -1) of another row that names one of them is removed — the row's surviving entries keep their
+        order at the front, the freed slots become -1 / -1 / -1.0.  A loader alone has no event table, so the t
+        column drops the slots e_id drops (TgnEngine.forget_nodes re-ranks it from the table; the two agree on a
+        time-ordered stream).  Returns {"nodes", "ring_slots", "ring_rows"}; bumps version.  An id outside [0, N):
+        ValueError; a valid slot naming a node outside [0, N): RuntimeError; both with the ring untouched.  An empty
+        list is a no-op.  A loader bound to a TgnEngine is handled by the engine (forget_nodes), which clears the
+        model's rows and the message stores with it."""
+        from . import tgn
+        ids = torch.as_tensor(ids).to(self.device, torch.long).contiguous().view(-1)
+        out = dict(nodes=0, ring_slots=0, ring_rows=0)
+        N = self.num_nodes
+        if not tgn.check_forget_args(N, ids.numel()):
+            return out
+        nb = int(_lib.lib().tgnx_tgn_forget_ws_bytes(ctypes.byref(tgn.TgnConfig(num_nodes=N))))
+        if nb == 0:
+            raise RuntimeError(f"tgnx_tgn_forget_ws_bytes: {_lib.lib().tgnx_last_error().decode()}")
+        ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        _lib.call("tgnx_ring_forget", _lib.ptr(self.neighbors), _lib.ptr(self.e_id), _lib.ptr(self.t), 0, 0, N,
+                  self.size, _lib.ptr(ids), ids.numel(), _lib.ptr(ws), nb, _lib.stream(self.device))
+        rec = ws[:64].view(torch.int64).tolist()      # (the call's kernels checked it too: a bad record stored nothing)
+        if rec[4]:
+            if bool(((ids < 0) | (ids >= N)).any()):
+                raise ValueError(f"LastNeighborLoader.forget: node ids must be in [0, {N}); nothing was changed")
+            raise RuntimeError(f"LastNeighborLoader.forget: {rec[4]} ring slots name a node outside [0, {N}); nothing "
+                               "was changed")
+        self.version += 1
+        return {k: int(rec[i]) for i, k in enumerate(out)}
 
     def _workspace(self, q: int) -> torch.Tensor:
         if q > self._ws_q:

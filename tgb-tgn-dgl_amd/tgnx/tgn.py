@@ -468,6 +468,22 @@ def check_compact_args(num_events: int, upto=None, capacity=None, world: int = 1
     return upto
 
 
+def check_forget_args(num_nodes: int, n_ids: int, world: int = 1, dp: bool = False) -> bool:
+    """Whether forget_nodes has anything to do (n_ids > 0), or ValueError: one device, a node space to forget from,
+    fewer than 2^31 ids (duplicates are allowed, so the list may be longer than num_nodes)."""
+    if world > 1 or dp:
+        raise ValueError("forget_nodes: one device only (world > 1 / the data-parallel step forms are not built)")
+    num_nodes, n_ids = int(num_nodes), int(n_ids)
+    if num_nodes < 1:
+        raise ValueError(f"forget_nodes: num_nodes = {num_nodes}")
+    if n_ids < 0 or n_ids >= MAX_NODES:
+        raise ValueError(f"forget_nodes: {n_ids} ids; an id list holds fewer than 2^31")
+    return n_ids > 0
+
+
+FORGET_COUNTS = ("nodes", "ring_slots", "ring_rows", "store_entries")    # record words 0..3 of tgnx_tgn_forget_plan
+
+
 def compact_capacity(n_live: int, capacity=None) -> int:
     """Row capacity of the compacted table: `capacity` when given (ValueError below n_live), else what grown_capacity
     gives a full table of n_live rows for one more row — max(n_live + 1, 1.5 x n_live) — so that the next append does
@@ -591,7 +607,12 @@ class TgnEngine:
     the node space in place — memory, last_update, node_gen, the ring, the stores and the workspace move into larger
     allocations (tgnx_tgn_grow_nodes), old rows bit for bit, new rows as reset_state leaves them — and cfg.num_nodes
     stays the logical count over a row capacity (node_capacity, reserve_nodes).  Captured graphs are dropped, the
-    resident bindings are made again."""
+    resident bindings are made again.
+
+    Nodes that leave (world 1): forget_nodes(ids) makes a node's memory, stores and ring row a never-seen node's and
+    removes every other node's ring slots and stored messages that name it, in place (tgnx_tgn_forget_plan / _apply);
+    what its past messages did to its partners' memory stays.  Bindings and graphs are dropped as a compaction drops
+    them."""
 
     def __init__(self, model: TGNModel, loader, events: dict, optimizer: TgnAdam | None = None,
                  dst_nodes=None, seed: int = 0, rank: int = 0, world: int = 1, data_parallel: bool | None = None):
@@ -1160,6 +1181,92 @@ class TgnEngine:
         kept = self._compact_apply(ws, n_live, cap)
         self._emb_moved(self.cfg.num_nodes, lv)
         return kept
+
+    # ------------------------------------------------------------------ forgetting nodes
+    def _forget_plan(self, ids: torch.Tensor):
+        """tgnx_tgn_forget_plan for the id tensor; returns (workspace, record as a list of 8 ints) after one host
+        read.  Writes only the workspace."""
+        nb = int(_lib.lib().tgnx_tgn_forget_ws_bytes(ctypes.byref(self.cfg)))
+        if nb == 0:
+            raise RuntimeError(f"tgnx_tgn_forget_ws_bytes: {_lib.lib().tgnx_last_error().decode()}")
+        ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+        _lib.call("tgnx_tgn_forget_plan", ctypes.byref(self.cfg), ctypes.byref(self._buffers(0)), self.num_events,
+                  _p(ids), ids.numel(), _p(ws), nb, self._stream())
+        return ws, ws[:64].view(torch.int64).tolist()
+
+    def _forget_apply(self, ws: torch.Tensor) -> None:
+        """Drop the bindings, bump loader.version and run tgnx_tgn_forget_apply on a clean plan's workspace."""
+        self._drop_bindings()
+        lv = getattr(self.loader, "version", 0)
+        self.loader.version = lv + 1
+        flags = self._emb_flags if self._emb_tab is not None else None
+        _lib.call("tgnx_tgn_forget_apply", ctypes.byref(self.cfg), ctypes.byref(self._buffers(0)), self.num_events,
+                  _p(ws), ws.numel(), _p(flags), self._stream())
+        # (the table's record of the loader version follows: only the marked rows are stale)
+        self._emb_moved(int(self.cfg.num_nodes), lv)
+
+    @torch.no_grad()
+    def forget_nodes(self, ids, *, compact: bool = False, drop_candidates: bool = False) -> dict:
+        """Erase the nodes `ids` (any integer sequence / tensor; duplicates allowed) from the stream state in place.
+
+        Own rows: memory, last_update and node_gen of a forgotten node become 0, its store runs empty and its ring row
+        neighbors -1 / e_id -1 / t -1.0 — bit for bit the row grow_nodes gives a node that has never been seen.  Other
+        nodes: every valid ring slot (e_id >= 0 and neighbors != -1) that names a forgotten node is removed, the row's
+        surviving (e_id, neighbors) pairs keep their order at the front and the rest of the row becomes (-1, -1); its
+        t column becomes ev_t[e_id] of the survivors ranked descending (ties by slot) with -1.0 behind them — on a
+        time-ordered stream that is the old column without the removed slots, on a stream whose t is shuffled it
+        repairs the column to the kept events' times.  Every store entry whose event has a forgotten node at the
+        other end is dropped and the run packed in place (offset kept, count reduced; an emptied run becomes {0, 0}).
+        A ring row or run that loses nothing is not written.  Nothing else moves: ctl, the batch cursor, parameters,
+        Adam moments and the event table stay; the rows only the forgotten nodes kept alive are dead, and
+        compact_events() (compact=True runs it straight away, with its default upto) retires every observed row with
+        an endpoint in ids.  Rows appended but not observed yet are not examined: filter them before observing, and
+        note that a default compaction retires them (compact_events: upto).
+
+        What is NOT undone: a partner's memory vector has already folded the node's past messages in through the
+        memory updater, and the parameters were trained on its events.  Nothing is retrained or recomputed.
+
+        The node stays in the node space: ids are not renumbered and it may be observed again (an id reused).  It
+        also stays a default candidate of recommend / rank and a train negative, scoring as a never-seen node does,
+        unless drop_candidates=True removes ids from dst_nodes (None becomes every node but ids; one more host read
+        for the mask select; ValueError, with nothing changed, if no candidate would be left).
+
+        Returns {"nodes": distinct ids, "ring_slots": slots removed from other nodes' rows, "ring_rows": rows that
+        lost one, "store_entries": entries dropped from other nodes' runs}, and "kept" (compact_events' result) with
+        compact=True.  An empty id list is a no-op: zeros, nothing launched, compacted or dropped.
+
+        Like compact_events, everything that captured a pointer or names a batch prepared from the old state is
+        dropped — the captured train and eval graphs, the plan table, the resident train and eval bindings (not made
+        again): bind again.  loader.version is bumped.  With the embedding table enabled, the forgotten nodes and the
+        rewritten ring rows are marked stale; the next refresh re-embeds them and their ring dependents only.
+
+        An id outside [0, N): ValueError.  A ring slot, store run or arena entry that names an event or node out of
+        range is counted on the device, never dereferenced: RuntimeError.  Both with the engine untouched.  One
+        device only (ValueError at world > 1 / the data-parallel forms).  One host read (two on the error path)."""
+        ids = self._ids(ids)
+        if not check_forget_args(self.cfg.num_nodes, ids.numel(), self.world, self.dp):
+            return dict.fromkeys(FORGET_COUNTS, 0)
+        self._settle()
+        N = int(self.cfg.num_nodes)
+        ws, rec = self._forget_plan(ids)
+        if rec[4]:
+            if bool(((ids < 0) | (ids >= N)).any()):
+                raise ValueError(f"forget_nodes: node ids must be in [0, {N}); nothing was changed")
+            raise RuntimeError(f"forget_nodes: {rec[4]} event ids / node ids / store runs out of range in the ring or "
+                               "the message stores; nothing was changed")
+        pool = None
+        if drop_candidates:
+            pool = torch.arange(N, device=self.dev) if self.dst_nodes is None else self.dst_nodes
+            pool = pool[~torch.isin(pool, ids)].contiguous()
+            if pool.numel() == 0:
+                raise ValueError("forget_nodes: drop_candidates would leave no candidate; nothing was changed")
+        self._forget_apply(ws)
+        if pool is not None:
+            self.dst_nodes = pool
+        out = {k: int(rec[i]) for i, k in enumerate(FORGET_COUNTS)}
+        if compact:
+            out["kept"] = self.compact_events()
+        return out
 
     @torch.no_grad()
     def stream_state(self) -> dict:

@@ -31,6 +31,8 @@ updates the stores, the memory and the ring in eval order.
       after the model was built (TgnEngine.grow_nodes); observe_grow(...) is observe() that does it from the ids it is given
   compact(model, neighbor_loader, upto=None, capacity=None) -> kept: retire the event-table rows nothing references
       and renumber the rest in order (TgnEngine.compact_events); kept[new] = old
+  forget(model, neighbor_loader, ids, compact=False, drop_candidates=False) -> counts: erase nodes from memory, ring
+      and stores in place (TgnEngine.forget_nodes)
   save_stream(model, neighbor_loader, f) / load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
       the whole stream state (table, memory, stores, ring, ctl; TgnEngine.stream_state) to / from a torch.save file
 
@@ -358,6 +360,24 @@ def compact(model, neighbor_loader, upto=None, capacity=None):
     kept = eng.compact_events(upto=upto, capacity=capacity)
     neighbor_loader.cur_e_id = eng.num_events
     return kept
+
+
+@torch.no_grad()
+def forget(model, neighbor_loader, ids, compact=False, drop_candidates=False):
+    """Erase the nodes `ids` from the stream state of the engine train() / test() attached to the model
+    (TgnEngine.forget_nodes): their memory, stores and ring rows become a never-seen node's, every other node's ring
+    slots and stored messages that name them are removed, and compact=True retires the event rows only they kept alive.
+    What their past messages already did to their partners' memory stays.  Straight after train() the memory is
+    switched to eval first, as observe() does (the flush folds the stored messages in; forgetting before it would only
+    drop them).  drop_candidates=True also removes ids from the engine's dst_nodes.  Returns forget_nodes' counts.  The
+    train / eval bindings and graphs of the loops above are dropped: train() / test() bind again."""
+    eng = _bound_engine(model, neighbor_loader, "forget")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    out = eng.forget_nodes(ids, compact=compact, drop_candidates=drop_candidates)
+    neighbor_loader.cur_e_id = eng.num_events
+    return out
 
 
 @torch.no_grad()
