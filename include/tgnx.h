@@ -484,6 +484,44 @@ int tgnx_tgn_train_fwd_bwd_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers
                               int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                               int32_t dropout, int32_t prefetched, int32_t parity, int32_t apply_prev, float* rows,
                               int64_t nrows, void* stream);
+/* The launch plan of a train step (host only: no device, no buffers; as tgnx_block_ids_host).  Every train entry
+ * point above decides in one place which launches it issues, how big they are and what rides in them; this returns
+ * those decisions, so that they can be pinned without a GPU (tests/test_step_plan_cpu.py).  The mode as the entry
+ * points spell it: fuse_adam (tgnx_tgn_train_step*), world (0: no device cursor; >= 1: a resident step of that
+ * world), prefetch (TGNX_TGN_PREFETCH_*), caller_scans (tgnx_tgn_train_fwd_bwd_split), parity (-1: one scan-output
+ * set; 0 / 1: _pp).  xrows / plan_table: that buffer is set; flags: tgnx_tgn_buffers.flags.  out: one record per
+ * launch label, in launch order (TGNX_TGN_STEP_LAUNCHES of them); a launch that is not issued has only its label.
+ * grid / block in workgroups / threads, lds = the dynamic LDS bytes of the launch, kernel = which instance the label
+ * launches (TGNX_TGN_AGG_*, _PRED_*, _ATTB_*, _FIXUP_*; tgn_gru_edge: 1 = with conv2's lin_edge; tgn_wgrad_dz0 /
+ * tgn_wgrad3: 1 = the launch carries the next batch's ScanJob; else 0). */
+#define TGNX_TGN_STEP_LAUNCHES 21
+#define TGNX_TGN_STEP_LABELS                                                                                        \
+  "tgn_mark", "tgn_scan", "tgn_gather", "tgn_agg_emit", "tgn_gru_edge", "tgn_proj", "tgn_attn_fwd", "tgn_proj2",    \
+      "tgn_attn_fwd2", "tgn_pred_train", "tgn_emb_update", "tgn_emb_update_gru", "tgn_attn_bwd2", "tgn_kv_reduce2", \
+      "tgn_dh1", "tgn_attn_bwd", "tgn_wgrad_dz0", "tgn_wgrad3", "tgn_scan_early", "tgn_fixup_update", "tgn_scan_next"
+#define TGNX_TGN_PREFETCH_PLAIN 0    /* not pipelined */
+#define TGNX_TGN_PREFETCH_PREPARED 1 /* pipelined, prefetched = 1 */
+#define TGNX_TGN_PREFETCH_FIRST 2    /* pipelined, prefetched = 0: the step prepares its own batch first */
+#define TGNX_TGN_AGG_ENC_FILL 0 /* tgn_enc_fill (gather-ahead) */
+#define TGNX_TGN_AGG_LAST 1     /* tgn_agg_emit<0> */
+#define TGNX_TGN_AGG_MEAN 2     /* tgn_agg_emit<1> (msg_dim <= 192) */
+#define TGNX_TGN_AGG_ANY 3      /* tgn_agg_emit<-1> */
+#define TGNX_TGN_PRED_RING10 0 /* tgn_pred_train<true, 10> */
+#define TGNX_TGN_PRED_RING 1   /* tgn_pred_train<true, 16> */
+#define TGNX_TGN_PRED_2HOP 2   /* tgn_pred_train<false> */
+#define TGNX_TGN_ATTB_EB10_REP 0 /* tgn_attn_bwd<10, 4> */
+#define TGNX_TGN_ATTB_EB16_REP 1 /* tgn_attn_bwd<16, 4> */
+#define TGNX_TGN_ATTB_EB10 2     /* tgn_attn_bwd<10, 1> */
+#define TGNX_TGN_ATTB_EB16 3     /* tgn_attn_bwd<16, 1> */
+#define TGNX_TGN_FIXUP_1HOP 0   /* TrainTail<false>, 4 weight gradients */
+#define TGNX_TGN_FIXUP_GATHER 1 /* TrainTail<true>: the next batch's gather rides */
+#define TGNX_TGN_FIXUP_2HOP 2   /* TrainTail<false>, 6 weight gradients */
+typedef struct tgnx_tgn_launch {
+  int32_t label, issued, grid, block, lds, kernel;
+} tgnx_tgn_launch;
+int tgnx_tgn_step_plan(const tgnx_tgn_config* cfg, int32_t fuse_adam, int32_t world, int32_t prefetch,
+                       int32_t caller_scans, int32_t parity, int32_t xrows, int32_t plan_table, int32_t flags,
+                       tgnx_tgn_launch* out);
 /* tgnx_tgn_apply_rows + tgnx_tgn_train_update in one launch (data parallel, after the exchange). */
 int tgnx_tgn_apply_rows_update(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, float* rows, int64_t nrows,
                                void* stream);

@@ -1151,7 +1151,7 @@ __device__ __forceinline__ PlanOut plan_view(const Ctx& c, int64_t start) {
 // the batch's events).  Resident train steps: every workgroup takes the batch from the step counters
 // and WG0 writes the descriptor into ctl for the later launches (no workgroup of this launch reads it).
 // scan_body: workgroup `role` of it (0: walks, 1 .. 2 pplan: plans), any workgroup size T with the
-// graph's bitmap words <= 2 T when scan_direct (scan_folds), LDS at smem (tgn_scan_smem)
+// graph's bitmap words <= 2 T when scan_direct (rides, `fold`), LDS at smem (tgn_scan_smem)
 // ahead: the batch `ahead` past the step counters' (1: the early scan of tgnx_tgn_train_step_pp, before this
 // step's counter advance); wdesc: write the batch descriptor into ctl (not while this step's launches still
 // read it); LW: capacity of the listed walk's LDS word list (>= 2 x the workgroup size); WPT: bitmap words per thread
@@ -4604,7 +4604,7 @@ struct ScanJob {
   }
 };
 // tail blocks of the train step's fixup launch: [0, nscan) the next batch's scan (pipelined steps whose
-// scan fits the launch's LDS and 256-thread workgroups, scan_folds; `nxt` = the live Ctx), then the
+// scan fits the launch's LDS and 256-thread workgroups, StepPlan::fold; `nxt` = the live Ctx), then the
 // Δt-encoding reduction (nte blocks), then the memory / last_update half of update_state (nmem blocks;
 // nothing in the fixup reads memory).  te.c is the fixup's view (fixup_view).
 // wdesc (tgnx_tgn_train_step_pp, whose next batch was scanned earlier in the step): the first Δt block also
@@ -5249,9 +5249,11 @@ using AttnBwdFn = void (*)(Ctx, int, int, int, Ctx);
 #ifndef TGNX_ATTB_EB10_2HOP
 #define TGNX_ATTB_EB10_2HOP 1  // 2 hops: the attention backward in 10-edge load batches for K <= 10 (0: 16-edge batches)
 #endif
-static AttnBwdFn attn_bwd_fn(int K, int rep, bool two = false) {
-  if (rep == TGNX_DZC_REP && TGNX_DZC_REP > 1) return K <= 10 ? tgn_attn_bwd<10, TGNX_DZC_REP> : tgn_attn_bwd<ATT_EB, TGNX_DZC_REP>;
-  return K <= 10 && (!two || TGNX_ATTB_EB10_2HOP) ? tgn_attn_bwd<10, 1> : tgn_attn_bwd<ATT_EB, 1>;
+static const AttnBwdFn attn_bwd_fns[4] = {tgn_attn_bwd<10, TGNX_DZC_REP>, tgn_attn_bwd<ATT_EB, TGNX_DZC_REP>, tgn_attn_bwd<10, 1>,
+                                           tgn_attn_bwd<ATT_EB, 1>};
+static int attn_bwd_id(int K, int rep, bool two) {  // (index into attn_bwd_fns: TGNX_TGN_ATTB_*)
+  if (rep == TGNX_DZC_REP && TGNX_DZC_REP > 1) return K <= 10 ? TGNX_TGN_ATTB_EB10_REP : TGNX_TGN_ATTB_EB16_REP;
+  return K <= 10 && (!two || TGNX_ATTB_EB10_2HOP) ? TGNX_TGN_ATTB_EB10 : TGNX_TGN_ATTB_EB16;
 }
 // integer knob from the environment (host, read once by the caller's static), else the build default
 static inline int env_int(const char* name, int def) {
@@ -5279,18 +5281,20 @@ static int pred_groups(int B) {
   const int per = (B + ncu - 1) / ncu;
   return (B + per - 1) / per;
 }
-// the GRU of a node list (eval update / flush): messages -> GRUCell (X, Z0 rows 0..n)
+// the GRU of a node list (eval update / flush): messages -> GRUCell (X, Z0 rows 0..n); its two launches' sizes
+static int gru_list_blocks(int mcap) { return gridn(mcap, 4, 2048); }
+static GemmShape shp_gru_list(int mcap, int G, int D, int Qm, const int* cnt) { return gemm_shape<G32L>(mcap, G * D, Qm + D, cnt); }
 template <int CELL>
 static void gru_list_c(const Ctx& c, const int64_t* list, const int* list_cnt, int n_host, int64_t base, int mcap,
                        hipStream_t s, bool emb = false) {
   using Cl = CellOps<CELL>;
   if (emb)   // DyRep embedding messages (update of src ∪ dst only)
-    tgn_agg_emit<-1, true><<<gridn(mcap, 4, 2048), 256, 0, s>>>(c, 2, 0, list, list_cnt, n_host, base);
+    tgn_agg_emit<-1, true><<<gru_list_blocks(mcap), 256, 0, s>>>(c, 2, 0, list, list_cnt, n_host, base);
   else if (c.aggr == 0)
-    tgn_agg_emit<0><<<gridn(mcap, 4, 2048), 256, 0, s>>>(c, 2, 0, list, list_cnt, n_host, base);
+    tgn_agg_emit<0><<<gru_list_blocks(mcap), 256, 0, s>>>(c, 2, 0, list, list_cnt, n_host, base);
   else
-    tgn_agg_emit<-1><<<gridn(mcap, 4, 2048), 256, 0, s>>>(c, 2, 0, list, list_cnt, n_host, base);
-  const GemmShape g1 = gemm_shape<G32L>(mcap, Cl::G * c.D, c.Qm + c.D, list_cnt);
+    tgn_agg_emit<-1><<<gru_list_blocks(mcap), 256, 0, s>>>(c, 2, 0, list, list_cnt, n_host, base);
+  const GemmShape g1 = shp_gru_list(mcap, Cl::G, c.D, c.Qm, list_cnt);
   gemm_launch<G32L>(g1, LoadGruA{c.X, c.mem, list ? list : c.nid, base, c.Qm, c.D, list ? 0 : 1}, Cl::w(c),
                     Cl::epi(c, list, base), nullptr, s);
 }
@@ -5433,29 +5437,245 @@ static void set_cursor(Ctx& c, const Cursor& a) {
   c.adv_world = a.world;
   c.adv_seed = a.seed;
 }
-static void train_scan(hipStream_t s, const Ctx& c, const Caps& k);  // (below, beside tgnx_tgn_scan_next)
-// pipe (resident world-1 fused steps only): 0 = plain step; 1 = pipelined, this batch already marked and
-// scanned by the previous pipelined step; 2 = pipelined, mark + scan this batch first.  A pipelined step
-// marks the next batch inside tgn_pred_train and scans it after its own last launch.
-extern "C++" {  // (inside the extern "C" block: the cell-templated step)
-// the next batch's scan as 256-thread head workgroups of the fixup launch: its LDS within the launch's,
-// and (small graphs, walked directly) <= 2 bitmap words per thread
-// (k: the global batch, whose plans the scan sorts; kr: the rank's share, whose centres the walk stages)
-static inline bool scan_rides(const Ctx& c, const Caps& k, const Caps& kr, size_t lds) {
-  return tgn_scan_smem(k.B) <= lds && (size_t)3 * kr.B * 12 <= lds && (!scan_direct(c.words) || c.words <= 2 * 256);
+extern "C++" {  // (inside the extern "C" block: the step's mode, plan and cell-templated launcher)
+// ---------------------------------------------------------------- the train step: mode, plan, launcher
+// How a train step runs: everything its nine entry points differ in.
+enum class Prefetch {
+  Plain,        // not pipelined: the step marks + scans its own batch and leaves the next one alone
+  Prepared,     // pipelined, this batch already marked + scanned (gather-ahead: gathered) by the previous step
+  PrepareFirst  // pipelined, but this batch is marked + scanned (+ gathered) first
+};
+struct StepMode {
+  bool fuse_adam = false;          // Adam folded into the gradient writers (world 1)
+  const Cursor* cursor = nullptr;  // the device batch cursor of a resident step; none: the caller advanced the counters
+  Prefetch prefetch = Prefetch::Plain;
+  bool caller_scans = false;  // pipelined, but the next batch's scan is the caller's (tgnx_tgn_scan_next)
+  int parity = -1;            // parity-set steps: the scan-output set the step reads (0 / 1); -1: the one set
+  bool pipelined() const { return prefetch != Prefetch::Plain; }
+  bool prepares() const { return prefetch != Prefetch::Prepared; }  // the step marks + scans its own batch
+  bool parity_sets() const { return parity >= 0; }
+};
+// what the plan needs to know of the buffers and the config beyond the capacities
+struct StepFacts {
+  bool xrows, plan_table;  // the data-parallel row slots / the bound split's plan table are there
+  int flags;               // tgnx_tgn_buffers.flags
+  int64_t words;           // bitmap words of the node marking
+  int pplan, K;            // plan partitions of the global batch; ring size
+  bool evj;                // the per-event ring-slot lists exist (1 hop, ring <= 16)
+  int aggr, emb, layers, cell;
+};
+static StepFacts step_facts(const tgnx_tgn_config* cfg, bool xrows, bool plan_table, int flags) {
+  const int layers = cfg_layers(cfg);
+  return StepFacts{xrows,     plan_table,      flags,  (cfg->num_nodes + 31) / 32 + 1, plan_parts(cfg->max_batch), cfg->ring,
+                   layers == 1 && cfg->ring <= 16, cfg->aggr, cfg->emb_in_msg,          layers,                     cfg->updater};
 }
-static inline bool scan_folds(const Ctx& c, const Caps& k, const Caps& kr) {
-  return scan_rides(c, k, kr, (size_t)GEMM_FIX_SMEM * 4);
+// data parallel: the rank's share ceil(B / world) of the global batch sets every per-rank capacity that
+// sizes a grid or a GEMM shape (roots, sampled nodes / edges, predictor rows, update list): grids sized
+// from the global batch launched ~W x the workgroups a rank needs (tgn_pred_train at world 8: 1,600
+// blocks for 200 events).  The global batch keeps what replays it whole on every rank (ring insert,
+// store update, their plans).  World 1 and the advance-driven form (world read on the device): kr == k.
+static Caps rank_caps(const tgnx_tgn_config* cfg, int world) {
+  tgnx_tgn_config r = *cfg;
+  r.max_batch = (int)((cfg->max_batch + world - 1) / world);
+  return make_caps(&r);
 }
-// pp >= 0 (tgnx_tgn_train_step_pp, world 1, 1 hop): the step reads scan-output set pp; the next batch is marked
-// in the predictor launch and scanned into set 1 - pp inside the k / v reduction launch (its outputs are then
-// written while this step's later launches still read set pp's), the fixup launch only writes its descriptor
+// the step's direct GEMMs (the deferred split-K ones: shp_dW* above); cnt: the step counters (null: capacity shapes)
+static const int* cnt_at(const int* cnt, int w) { return cnt ? cnt + w : nullptr; }
+static GemmShape shp_gru(const Caps& k, const int* cnt) { return with_cap(gemm_shape<G32L>(k.Mtr, k.G * k.D, k.Qm + k.D, cnt_at(cnt, CNT_M)), TGNX_GRU_CAP); }
+static GemmShape shp_edge(const Caps& k, const int* cnt, int cap) { return with_cap(gemm_shape<G32>(k.Etr, k.HC, k.D + k.d, cnt_at(cnt, CNT_E)), cap); }
+static GemmShape shp_edge2(const Caps& k, const int* cnt) { return gemm_shape<G32>(k.E1tr, k.HC, k.D + k.d, cnt_at(cnt, CNT_E1)); }
+static GemmShape shp_proj(const Caps& k, const int* cnt) { return gemm_shape<G32>(k.Mtr, 4 * k.HC, k.D, cnt_at(cnt, CNT_M)); }
+static GemmShape shp_proj2(const Caps& k, const int* cnt) { return gemm_shape<G32>(k.Rtr, 4 * k.HC, k.HC, cnt_at(cnt, CNT_R)); }
+static GemmShape shp_denc2(const Caps& k, const int* cnt) { return gemm_shape<G32>(k.E1tr, k.D, k.HC, cnt_at(cnt, CNT_E1)); }
+static GemmShape shp_dh1(const Caps& k, const int* cnt) { return gemm_shape<G32L>(k.Rtr, k.HC, 4 * k.HC, cnt_at(cnt, CNT_R)); }
+static GemmShape shp_denc(const Caps& k, const int* cnt, int cap) { return with_cap(gemm_shape<G32>(k.Etr, k.D, k.HC, cnt_at(cnt, CNT_E)), cap); }
+static GemmShape shp_dz0(const Caps& k, const int* cnt, int cap) { return with_cap(gemm_shape<G32L>(k.Mtr, k.D, 4 * k.HC, cnt_at(cnt, CNT_M)), cap); }
+static GemmShape shp_dxe(const Caps& k, const int* cnt, int cap) { return with_cap(gemm_shape<GXE>(k.Mtr, k.D, k.G * k.D, cnt_at(cnt, CNT_M)), cap); }
+
+// The step's launches in order, named by their TGNX_LAUNCH_CHECK labels (TGNX_TGN_STEP_* of include/tgnx.h).
+enum StepLaunch {
+  L_MARK, L_SCAN, L_GATHER, L_AGG_EMIT, L_GRU_EDGE, L_PROJ, L_ATTN_FWD, L_PROJ2, L_ATTN_FWD2, L_PRED, L_EMB_AGG, L_EMB_GRU,
+  L_ATTN_BWD2, L_KV_REDUCE2, L_DH1, L_ATTN_BWD, L_WGRAD_DZ0, L_WGRAD3, L_SCAN_EARLY, L_FIXUP, L_SCAN_NEXT, L_COUNT
+};
+static_assert(L_COUNT == TGNX_TGN_STEP_LAUNCHES, "include/tgnx.h names the step's launches");
+// a whole scan (walk + the 2 pplan plan workgroups) as a launch of its own
+static tgnx_tgn_launch scan_launch(int label, int pplan, int B) {
+  return tgnx_tgn_launch{label, 1, 1 + 2 * pplan, TGNX_SCAN_T, (int32_t)tgn_scan_smem(B), 0};
+}
+struct StepPlan {
+  bool two, ga, kvs;                                        // 2 hops; gather-ahead; the (dk, dv) sort fits the predictor's LDS
+  bool walk_bwd, scan_w3, plans_pred, scan6, walk_w3;       // parity sets: where the next batch's plans and walk ride
+  bool scan_next, fold;                                     // one set, pipelined: the step scans the next batch, inside the fixup launch
+  int edge_cap, md_cap;                                     // grid caps of the E x . and M x D GEMMs (per 200 events of the rank's batch)
+  int nmark, nevb, nedge, ngn, nge, ngat;                   // mark; agg_emit / GatherJob parts: event, edge, node blocks
+  int nring, nkv2, nmk, npl, nsrt;                                       // riding in the predictor launch: mark, plan, sort blocks
+  int ncb, ncb1, nkv, nwalk;                                // attention backward: centre / root blocks, (dk, dv) blocks, the walk
+  int nscanj, nst, nmem, nmem7;                             // dW_cell launch: ScanJob, store blocks, memory blocks (of them here)
+  int nfix, nscan, nte;                                           // fixup launch: scan blocks, Δt-reduction blocks
+  tgnx_tgn_launch L[L_COUNT];
+};
+
+// The one riding rule.  A piece of the next batch's scan rides in another launch as 256-thread workgroups when the
+// sort of plan_B events' plans (0: no plans, the walk alone) and the walk's staging of the rank's 3 Bk centres (12
+// bytes each) fit the launch's `lds` bytes and, on a small graph (walked directly), a thread holds <= wpt bitmap words.
+static bool rides(const StepFacts& f, int plan_B, int Bk, size_t lds, int wpt) {
+  return (plan_B == 0 || tgn_scan_smem(plan_B) <= lds) && (size_t)3 * Bk * 12 <= lds &&
+         (!scan_direct(f.words) || f.words <= (int64_t)wpt * 256);
+}
+
+// Where the next batch is prepared (k: the global batch, whose plans the scan sorts; kr: the rank's share, whose
+// centres the walk stages).  mark = tgn_mark's blocks, plans = the ring-insert / store plans, walk = the scan's
+// bitmap walk (role 0), gather = gather-ahead's GatherJob.  W3 = the dW_cell launch's 3 x MARK_LDS_WORDS x 4 bytes.
+//
+//   mode                        mark       plans + walk
+//   plain                       -          -            (each step: tgn_mark, tgn_scan of its own batch first)
+//   pipelined, one set          predictor  head blocks of the fixup launch if rides(k.B, kr.B, fixup LDS, 2) (`fold`),
+//                                          else tgn_scan_next after it; caller_scans: the caller's tgnx_tgn_scan_next
+//   parity sets, plan table     predictor  plans: the table.  Walk: 1 hop, rides(0, kr.B, W3, 2): attention-backward launch
+//                                          (`walk_bwd`); else rides(0, kr.B, W3, 8): ScanJob in the dW_cell launch
+//                                          (`scan_w3`); else tgn_scan_early after the dW_cell launch
+//   parity sets, no table       predictor  rides(k.B, kr.B, W3, 2): all of it as ScanJob in the dW_cell launch (`scan_w3`);
+//                                          else 2..TGNX_PLANS_IN_PRED partitions (data parallel: the global batch's 2 B
+//                                          keys) that fit the predictor launch's LDS: plans there (`plans_pred`), the
+//                                          walk alone as ScanJob; else tgn_scan_early
+//   gather-ahead                head blocks of the fixup launch, on the other parity's set (parity sets, world 1,
+//                               1 hop, GRU, LastAggregator, TGNMemory messages, Adam fused); a step that was not
+//                               prepared gathers for itself after its scan (tgn_gather), and every such step
+//                               starts with tgn_enc_fill (the Δt-encoding columns) instead of tgn_agg_emit
+//
+// Why.  A pipelined step marks the next batch beside the predictor's sort block (in the dz0 launch for graphs marked
+// through summary bitmaps: review-shaped 0.1040 vs 0.1037 ms, not kept).  A parity-set step scans the next batch
+// into set 1 - parity mid-step, while its own later launches still read set parity; the counters advance, and the
+// descriptor is written, in the fixup launch.  The scan rides in the dW_cell launch (TGNX_SCAN_AT 7; 6, the dz0
+// launch: 0.1005 vs 0.0965 ms).  The attention-backward walk holds 2 bitmap words per thread, the dW_cell launch's
+// ScanJob 8: its LDS word list takes the 2-hop comment-shaped walk's ~1,100 words, so 2 hops walk there —
+// comment-shaped A/B 0.2383 / 0.2397 ms against 0.2462 / 0.2459 for the pipelined step, 0.2504 / 0.2498 in the
+// attention backward; the wide walk in the attention backward cost the wiki step +0.9 %.  TGNX_PLANS_IN_PRED: its
+// define carries the data-parallel A/B.  In the one-set step SnapJob copies the descriptor and advances the counters
+// a launch before the fixup, so the scan folded into the fixup launch may rewrite them.
+static StepPlan plan_step(const Caps& k, const Caps& kr, const StepMode& m, const StepFacts& f) {
+  StepPlan p{};
+  const int D = k.D, K = f.K;
+  const bool ppm = m.parity_sets(), two = f.layers == 2, ptab = ppm && f.plan_table;
+  const size_t w3_lds = (size_t)3 * MARK_LDS_WORDS * 4;
+  p.two = two;
+  p.ga = f.cell == 0 && ppm && m.fuse_adam && !two && f.aggr == 0 && !f.emb && !f.xrows &&
+         !(f.flags & TGNX_TGN_NO_GATHER_AHEAD);
+  // 1 hop with the attention forward in the predictor: the attention backward computes each edge's (dk, dv) where
+  // it sums them (kv_edge_body, after the predictor's sort block), so there is no k / v reduction launch and the
+  // GEMMs that need only dE ride in a later launch (2 hops: the outer level; conv2 keeps its reduction job)
+  p.kvs = !two && (size_t)kr.Mtr + 1 <= tgn_pred_smem(D) / 4;
+  p.walk_bwd = ptab && !two && rides(f, 0, kr.B, w3_lds, 2);
+  p.scan_w3 = ppm && !p.walk_bwd && rides(f, ptab ? 0 : k.B, kr.B, w3_lds, ptab ? 8 : 2);
+  static const int plans_in_pred = env_int("TGNX_PLANS_IN_PRED", TGNX_PLANS_IN_PRED);  // (runtime A/B switch)
+  p.plans_pred = ppm && !ptab && !p.scan_w3 && plans_in_pred && f.pplan > 1 && f.pplan <= plans_in_pred &&
+                 2 * k.B <= PRED_PLAN_MAXE * 256 && rides(f, kr.B, kr.B, w3_lds, 2) &&
+                 tgn_scan_smem(k.B) <= tgn_pred_smem(TDMAX);
+  p.scan6 = p.scan_w3 && TGNX_SCAN_AT == 6;
+  p.walk_w3 = (p.scan_w3 || p.plans_pred) && !p.walk_bwd;
+  p.scan_next = m.pipelined() && !m.caller_scans && !ppm;
+  p.fold = p.scan_next && rides(f, k.B, kr.B, (size_t)GEMM_FIX_SMEM * 4, 2);
+  p.edge_cap = cap_per200("TGNX_EDGE_CAP200", TGNX_EDGE_CAP200, kr.B);
+  p.md_cap = cap_per200("TGNX_MD_CAP200", TGNX_MD_CAP200, kr.B);
+  p.nmark = gridn(3 * kr.B * 16, 256);
+  p.nevb = gridn(3 * kr.B * (f.evj ? 16 : 1), 256);
+  p.nedge = gridn((int64_t)kr.Rtr * K, 4, TGNX_AGG_EDGE_CAP);
+  p.ngn = gridn(kr.Mtr, 4, TGNX_GA_NODE_CAP);
+  p.nge = gridn((int64_t)kr.Rtr * K, 4, TGNX_GA_EDGE_CAP);
+  p.ngat = p.nevb + p.ngn + p.nge;
+  p.nring = gridn(2 * k.B, 4);               // ring merge blocks (gru_edge launch)
+  p.nkv2 = gridn(kr.E1tr, KVR_CH, 1 << 20);  // conv2's (dk, dv) reduction blocks
+  p.nmk = m.pipelined() ? p.nmark : 0;
+  p.npl = p.plans_pred ? 2 * f.pplan : 0;
+  p.nsrt = p.kvs ? 1 : 0;
+  p.ncb = gridn(kr.Rtr, 4, 1 << 20);
+  p.ncb1 = gridn(kr.R1tr, 4, 1 << 20);
+  p.nkv = gridn(kr.Etr, KVE_CH, 1 << 20);
+  const int nred = gridn(3 * D + 2, 4);  // the predictor's reductions, riding in the attention backward of its level
+  p.nwalk = p.walk_bwd ? 1 : 0;
+  p.nscanj = p.walk_bwd ? 0 : p.plans_pred || ptab ? 1 : 1 + 2 * f.pplan;
+  p.nst = gridn(2 * k.B, 256);
+  p.nmem = gridn(kr.Ucap, 4, 1024);
+  p.nmem7 = p.ga ? p.nmem : 0;  // (gather-ahead: the memory / last_update half rides in the dW_cell launch, not in the fixup)
+  p.nscan = p.fold ? 1 + 2 * f.pplan : 0;
+  p.nte = (2 * D + 63) / 64;
+
+  auto put = [&](int id, bool on, int grid, int block = 256, size_t lds = 0, int kernel = 0) {
+    p.L[id] = on ? tgnx_tgn_launch{id, 1, grid, block, (int32_t)lds, kernel} : tgnx_tgn_launch{id, 0, 0, 0, 0, 0};
+  };
+  auto put_scan = [&](int id, bool on) { p.L[id] = on ? scan_launch(id, f.pplan, k.B) : tgnx_tgn_launch{id, 0, 0, 0, 0, 0}; };
+  auto nb = [](const GemmShape& g) { return gemm_blocks(g); };
+  auto tiles = [](const GemmShape& g) { return g.tiles_m * g.tiles_n; };
+  put(L_MARK, m.prepares(), p.nmark);
+  put_scan(L_SCAN, m.prepares());
+  put(L_GATHER, p.ga && m.prepares(), p.ngat);
+  if (p.ga)
+    put(L_AGG_EMIT, true, gridn(kr.Etr + kr.Mtr, 4, TGNX_ENC_CAP), 256, 0, TGNX_TGN_AGG_ENC_FILL);
+  else
+    put(L_AGG_EMIT, true, p.nevb + p.nedge + gridn(kr.Mtr, 4, TGNX_AGG_NODE_CAP), 256, 0,
+        f.aggr == 0 ? TGNX_TGN_AGG_LAST : f.aggr == 1 && k.d <= 192 ? TGNX_TGN_AGG_MEAN : TGNX_TGN_AGG_ANY);
+  put(L_GRU_EDGE, true, p.nring + nb(shp_gru(kr, nullptr)) + nb(shp_edge(kr, nullptr, p.edge_cap)) +
+                            (two ? nb(shp_edge2(kr, nullptr)) : 0), 256, 0, two);
+  put(L_PROJ, true, nb(shp_proj(kr, nullptr)));
+  put(L_ATTN_FWD, two, p.ncb);
+  put(L_PROJ2, two, nb(shp_proj2(kr, nullptr)));
+  put(L_ATTN_FWD2, two, p.ncb1);
+  // the predictor: 1 hop with the attention forward inside it (per root, beside its weight staging), for a ring of
+  // <= 10 or more; 2 hops without
+  put(L_PRED, true, (two && pred_stages<false>() ? pred_groups(kr.B) : kr.B) + p.npl + p.nsrt + p.nmk,
+      64 * (two ? pred_waves<false>() : pred_waves<true>()),
+      std::max({!two || pred_stages<false>() ? tgn_pred_smem(D) : (size_t)16, p.nmk ? w3_lds : (size_t)0,
+                p.npl ? tgn_scan_smem(k.B) : (size_t)0}),
+      two ? TGNX_TGN_PRED_2HOP : K <= 10 ? TGNX_TGN_PRED_RING10 : TGNX_TGN_PRED_RING);
+  put(L_EMB_AGG, f.emb != 0, gru_list_blocks(kr.Ucap));  // (gru_list_c over the update list)
+  put(L_EMB_GRU, f.emb != 0, nb(shp_gru_list(kr.Ucap, k.G, D, k.Qm, nullptr)));
+  put(L_ATTN_BWD2, two, p.ncb1 + nred, 256, 0, attn_bwd_id(K, 1, true));
+  put(L_KV_REDUCE2, two, p.nkv2 + nb(shp_dWe2(kr, nullptr)) + nb(shp_denc2(kr, nullptr)));
+  put(L_DH1, two, nb(shp_dh1(kr, nullptr)) + nb(shp_dWp2(kr, nullptr)));
+  put(L_ATTN_BWD, true, p.ncb + p.nkv + (two ? 0 : nred) + p.nwalk, 256, p.walk_bwd ? (size_t)3 * kr.B * 12 + 16 : 0,
+      attn_bwd_id(K, two ? 1 : TGNX_DZC_REP, two));
+  put(L_WGRAD_DZ0, true, (p.scan6 ? p.nscanj : 0) + nb(shp_dz0(kr, nullptr, p.md_cap)) + nb(shp_dWp(kr, nullptr)) +
+                             nb(shp_dWlp(kr, nullptr)), 256, 0, p.scan6);
+  const bool scanj_w3 = p.walk_w3 && !p.scan6;  // (kernel 1: the launch that carries the ScanJob)
+  put(L_WGRAD3, true, (scanj_w3 ? p.nscanj : 0) + nb(shp_dxe(kr, nullptr, p.md_cap)) + nb(shp_dWg(kr, nullptr)) +
+                          nb(shp_dWe(kr, nullptr)) + nb(shp_denc(kr, nullptr, p.edge_cap)) + 1 + p.nst + p.nmem7, 256, 0, scanj_w3);
+  put(L_SCAN_EARLY, ppm && !p.walk_w3 && !p.walk_bwd, ptab ? 1 : 1 + 2 * f.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B));
+  p.nfix = (tiles(shp_dWe(kr, nullptr)) + tiles(shp_dWp(kr, nullptr)) + tiles(shp_dWlp(kr, nullptr)) +
+                    tiles(shp_dWg(kr, nullptr)) + (two ? tiles(shp_dWp2(kr, nullptr)) + tiles(shp_dWe2(kr, nullptr)) : 0) + 7) & ~7;
+  put(L_FIXUP, true, p.nfix + (p.ga ? p.ngat + p.nte : p.nscan + p.nte + p.nmem), 256, 0,
+      p.ga ? TGNX_TGN_FIXUP_GATHER : two ? TGNX_TGN_FIXUP_2HOP : TGNX_TGN_FIXUP_1HOP);
+  put_scan(L_SCAN_NEXT, p.scan_next && !p.fold);
+  return p;
+}
+template <class... KA, class... A>
+static void launch_p(void (*kern)(KA...), const tgnx_tgn_launch& l, hipStream_t s, A... a) {
+  launch_k(kern, dim3(l.grid), dim3(l.block), (uint32_t)l.lds, s, a...);
+}
+// a gemmN launch at the plan's size (W: its waves-per-SIMD floor): the jobs must fill exactly the planned grid
+template <int W = 0, class... J>
+static int launch_jobs(const tgnx_tgn_launch& l, hipStream_t s, const J&... j) {
+  TGNX_CHECK_ARG((job_blocks(j) + ... + 0) == l.grid, "tgn: the jobs of launch %d do not fill its planned grid of %d", l.label, l.grid);
+  if constexpr (W > 0) launch_p(gemmN_kernel_w<W, J...>, l, s, j...);
+  else launch_p(gemmN_kernel<J...>, l, s, j...);
+  return TGNX_OK;
+}
+// the fixup launch at the plan's size: the weight gradients' tiles must be the nfix the plan counted
+template <class TAIL, class... F>
+static int launch_fixup(const tgnx_tgn_launch& l, int nfix, hipStream_t s, const TAIL& tail, int head, const F&... f) {
+  TGNX_CHECK_ARG(gemm_fix_range(f...) == nfix, "tgn: the fixup's tiles do not fill the planned %d", nfix);
+  launch_p(gemm_fixup_kernel<TAIL, F...>, l, s, tail, head, nfix, f...);
+  return TGNX_OK;
+}
+static void train_scan(hipStream_t s, const Ctx& c, const tgnx_tgn_launch& l);  // (below, beside tgnx_tgn_scan_next)
+
+// The launcher: argument checks, the Ctx views, the jobs and the launches; whether a launch is issued, how big it
+// is and what rides in it come from the plan.
 template <int CELL>
 static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t gen_neg, int32_t dropout,
-                             void* stream, bool fuse_adam, const Cursor* adv, int pipe, int pp) {
+                             void* stream, const StepMode& m) {
   using Cl = CellOps<CELL>;
-  const bool no_tail = (pipe & 4) != 0;  // pipelined, but the next batch's scan is the caller's (tgnx_tgn_scan_next)
-  pipe &= 3;
+  const Cursor* adv = m.cursor;
+  const bool fuse_adam = m.fuse_adam, ppm = m.parity_sets();
   Ctx c;
   Caps k;
   WsLay W;
@@ -5471,14 +5691,7 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
                    "(tgnx_tgn_train_fwd_bwd_resident + exchange + tgnx_tgn_train_update)");
     set_cursor(c, *adv);
   }
-  // data parallel: the rank's share ceil(B / world) of the global batch sets every per-rank capacity that
-  // sizes a grid or a GEMM shape (roots, sampled nodes / edges, predictor rows, update list): grids sized
-  // from the global batch launched ~W x the workgroups a rank needs (tgn_pred_train at world 8: 1,600
-  // blocks for 200 events).  The global batch keeps what replays it whole on every rank (ring insert,
-  // store update, their plans).  World 1 and the advance-driven form (world read on the device): kr == k.
-  tgnx_tgn_config cfg_r = *cfg;
-  if (adv) cfg_r.max_batch = (int)((cfg->max_batch + adv->world - 1) / adv->world);
-  const Caps kr = make_caps(&cfg_r);
+  const Caps kr = rank_caps(cfg, adv ? adv->world : 1);
   c.Bmax = kr.B;  // (the scan walk stages the rank's centres in LDS: 3 Bmax entries)
   TGNX_CHECK_ARG(buf->neg && buf->grads && buf->out_pos && buf->out_neg, "tgnx_tgn_train_fwd_bwd: null buffer");
   // DyRep embedding messages need every embedding of src ∪ dst on this rank: world 1 only
@@ -5497,10 +5710,9 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
     c.adf.keep_g = (buf->flags & TGNX_TGN_NO_GRAD_STORE) ? 0 : 1;
   }
   TGNX_CHECK_ARG(!gen_neg || (buf->dst_nodes && buf->n_dst > 0), "tgnx_tgn_train_fwd_bwd: no destination set");
-  TGNX_CHECK_ARG(pipe == 0 || adv, "tgnx_tgn_train_step_pipelined: resident steps only");
+  TGNX_CHECK_ARG(!m.pipelined() || adv, "tgnx_tgn_train_step_pipelined: resident steps only");
   c.gen_neg = gen_neg ? 1 : 0;
   c.drop = dropout && cfg->dropout > 0.f;
-  const bool ppm = pp >= 0;
   if (ppm && buf->plan_table) {  // the split's plans from the table built at binding (tgnx_tgn_plan_table)
     PlanTableKey pk{-1, -1, -1, -1, 0};
     bool known = false;
@@ -5522,155 +5734,106 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
     c.ptab = reinterpret_cast<const char*>(buf->plan_table);
     c.ptab_stride = plan_slot_bytes(k.B);
   }
-  Ctx cn;  // ppm: the other parity's set (the next batch's scan writes it)
+  Ctx cn;  // parity sets: the other parity's set (the next batch's scan writes it)
   if (ppm) {
-    TGNX_CHECK_ARG(pp <= 1 && pipe != 0 && !no_tail && adv && (!fuse_adam || adv->world == 1),
+    TGNX_CHECK_ARG(m.parity <= 1 && m.pipelined() && !m.caller_scans && adv && (!fuse_adam || adv->world == 1),
                    "tgnx_tgn_train_step_pp / tgnx_tgn_train_fwd_bwd_pp: a resident step, parity 0 or 1 "
                    "(Adam fused at world 1 only)");
     char* ws = reinterpret_cast<char*>(buf->ws);
-    cn = set_view(c, W, ws, 1 - pp);
-    c = set_view(c, W, ws, pp);
+    cn = set_view(c, W, ws, 1 - m.parity);
+    c = set_view(c, W, ws, m.parity);
     c.tagchk = 1;
   }
+  const StepPlan pl = plan_step(k, kr, m, StepFacts{c.xrows != nullptr, buf->plan_table != nullptr, buf->flags, c.words, c.pplan,
+                                                    c.K, c.evj != nullptr, c.aggr, c.emb, k.layers, CELL});  // (what the kernels read)
+  const tgnx_tgn_launch* L = pl.L;
+  const bool two = pl.two;
   hipStream_t s = as_stream(stream);
   const float* P = c.params;
   float* G = c.grads;
   const int D = c.D, HC = c.HC, Qm = c.Qm, d = c.d;
-  if (pipe != 1) {
-    const int nmark = gridn(3 * kr.B * 16, 256);
-    tgn_mark<true><<<nmark, 256, 0, s>>>(c, nmark);
+  if (L[L_MARK].issued) {
+    tgn_mark<true><<<L[L_MARK].grid, L[L_MARK].block, 0, s>>>(c, pl.nmark);
     TGNX_LAUNCH_CHECK("tgn_mark");
-    train_scan(s, c, k);
+    train_scan(s, c, L[L_SCAN]);
     TGNX_LAUNCH_CHECK("tgn_scan");
   }
-  const int nedge = gridn((int64_t)kr.Rtr * c.K, 4, TGNX_AGG_EDGE_CAP);
-  const int nevb = gridn(3 * kr.B * (c.evj ? 16 : 1), 256);
-  const int nagg = nevb + nedge + gridn(kr.Mtr, 4, TGNX_AGG_NODE_CAP);
   // gather-ahead (GatherJob): the parameter-free half of tgn_agg_emit ran in the previous step's fixup launch (or
-  // runs here, for a step that was not prefetched); tgn_enc_fill adds the Δt-encoding columns
-  const bool ga = CELL == 0 && ppm && fuse_adam && k.layers == 1 && c.aggr == 0 && !c.emb && !c.xrows &&
-                  !(buf->flags & TGNX_TGN_NO_GATHER_AHEAD);
-  const int ngn = gridn(kr.Mtr, 4, TGNX_GA_NODE_CAP), nge = gridn((int64_t)kr.Rtr * c.K, 4, TGNX_GA_EDGE_CAP);
-  const GatherJob gat{1, nevb, ngn, nge};
-  const int ngat = nevb + ngn + nge;
-  if (ga && pipe != 1) {
+  // runs here, for a step that was not prepared); tgn_enc_fill adds the Δt-encoding columns
+  const GatherJob gat{1, pl.nevb, pl.ngn, pl.nge};
+  if (L[L_GATHER].issued) {
     GatherJob g0 = gat;
     g0.ahead = 0;
-    launch_k(tgn_gather, dim3(ngat), dim3(256), 0, s, c, g0);
+    launch_p(tgn_gather, L[L_GATHER], s, c, g0);
     TGNX_LAUNCH_CHECK("tgn_gather");
   }
   probe_begin(TGNX_K_EDGE_META, s);
   const int64_t* nol = nullptr;
   const int* noc = nullptr;
-  if (ga)
-    launch_k(tgn_enc_fill, dim3(gridn(kr.Etr + kr.Mtr, 4, TGNX_ENC_CAP)), dim3(256), 0, s, c);
-  else if (c.aggr == 0)
-    launch_k(tgn_agg_emit<0>, dim3(nagg), dim3(256), 0, s, c, 0, nedge, nol, noc, 0, (int64_t)0, nevb);
-  else if (c.aggr == 1 && c.d <= 192)
-    launch_k(tgn_agg_emit<1>, dim3(nagg), dim3(256), 0, s, c, 0, nedge, nol, noc, 0, (int64_t)0, nevb);
+  if (L[L_AGG_EMIT].kernel == TGNX_TGN_AGG_ENC_FILL)
+    launch_p(tgn_enc_fill, L[L_AGG_EMIT], s, c);
+  else if (L[L_AGG_EMIT].kernel == TGNX_TGN_AGG_LAST)
+    launch_p(tgn_agg_emit<0>, L[L_AGG_EMIT], s, c, 0, pl.nedge, nol, noc, 0, (int64_t)0, pl.nevb);
+  else if (L[L_AGG_EMIT].kernel == TGNX_TGN_AGG_MEAN)
+    launch_p(tgn_agg_emit<1>, L[L_AGG_EMIT], s, c, 0, pl.nedge, nol, noc, 0, (int64_t)0, pl.nevb);
   else
-    launch_k(tgn_agg_emit<-1>, dim3(nagg), dim3(256), 0, s, c, 0, nedge, nol, noc, 0, (int64_t)0, nevb);
+    launch_p(tgn_agg_emit<-1>, L[L_AGG_EMIT], s, c, 0, pl.nedge, nol, noc, 0, (int64_t)0, pl.nevb);
   probe_end(TGNX_K_EDGE_META, s);
   TGNX_LAUNCH_CHECK("tgn_agg_emit");
   // GRU over every sampled node ‖ lin_edge over every sampled edge (‖ 2 hops: conv2's lin_edge over the
   // root edges)
   const LoadRowK ea{c.encE, kr.Etr, D + d, D + d};  // the edges' [cos enc | msg] rows (tgn_agg_emit, train)
-  const bool two = k.layers == 2;
-  const LoadAttrMap ea1{c.encE, c.e1_e2, D + d};  // root edge -> its outer edge's row
-  const int edge_cap = cap_per200("TGNX_EDGE_CAP200", TGNX_EDGE_CAP200, kr.B);
-  const int md_cap = cap_per200("TGNX_MD_CAP200", TGNX_MD_CAP200, kr.B);
-  const auto j_gru = gemm_job<G32L>(with_cap(gemm_shape<G32L>(kr.Mtr, Cl::G * D, Qm + D, c.cnt + CNT_M), TGNX_GRU_CAP),
-                                    LoadGruA{c.X, c.mem, c.nid, 0, Qm, D, 0}, Cl::w(c), Cl::epi_train(c),
-                                    (float*)nullptr);
-  const auto j_edge = gemm_job<G32>(with_cap(gemm_shape<G32>(kr.Etr, HC, D + d, c.cnt + CNT_E), edge_cap), ea,
-                                    LoadRowK{P + c.L.we, HC, D + d, D + d}, EpiStore{c.Ep, nullptr, HC, 0}, (float*)nullptr);
-  const BlockJob<RingMergeJob> j_ring{RingMergeJob{c}, gridn(2 * k.B, 4)};
+  const LoadAttrMap ea1{c.encE, c.e1_e2, D + d};    // root edge -> its outer edge's row
+  const auto j_gru = gemm_job<G32L>(shp_gru(kr, c.cnt), LoadGruA{c.X, c.mem, c.nid, 0, Qm, D, 0}, Cl::w(c),
+                                    Cl::epi_train(c), (float*)nullptr);
+  const auto j_edge = gemm_job<G32>(shp_edge(kr, c.cnt, pl.edge_cap), ea, LoadRowK{P + c.L.we, HC, D + d, D + d},
+                                    EpiStore{c.Ep, nullptr, HC, 0}, (float*)nullptr);
+  const BlockJob<RingMergeJob> j_ring{RingMergeJob{c}, pl.nring};
   probe_begin(TGNX_K_EDGE_FWD, s);
   if (two)
-    gemmN_launch(s, j_ring, j_gru, j_edge,
-                 gemm_job<G32>(gemm_shape<G32>(kr.E1tr, HC, D + d, c.cnt + CNT_E1), ea1,
-                               LoadRowK{P + c.L.we2, HC, D + d, D + d}, EpiStore{c.Ep2, nullptr, HC, 0}, (float*)nullptr));
+    rc = launch_jobs(L[L_GRU_EDGE], s, j_ring, j_gru, j_edge,
+                     gemm_job<G32>(shp_edge2(kr, c.cnt), ea1, LoadRowK{P + c.L.we2, HC, D + d, D + d},
+                                   EpiStore{c.Ep2, nullptr, HC, 0}, (float*)nullptr));
   else
-    gemmN_launch_w<TGNX_GRU_WAVES>(s, j_ring, j_gru, j_edge);
+    rc = launch_jobs<TGNX_GRU_WAVES>(L[L_GRU_EDGE], s, j_ring, j_gru, j_edge);
+  if (rc) return rc;
   probe_end(TGNX_K_EDGE_FWD, s);
   TGNX_LAUNCH_CHECK("tgn_gru_edge");
-  const int nmark = gridn(3 * kr.B * 16, 256);
-  // 1 hop with the attention forward in the predictor: the attention backward computes each edge's (dk, dv)
-  // where it sums them (kv_edge_body), so the k / v reduction launch is gone and the GEMMs that need only dE
-  // ride in a later launch
-  // (2 hops: the outer level, whose attention forward is tgn_attn_fwd; its edges keep the sampling order)
-  const bool kvf = true;  // (the separate k / v reduction launch: slower)
-  const bool kvs = !two && (size_t)kr.Mtr + 1 <= tgn_pred_smem(c.D) / 4;
-  c.kvf = 1;
-  c.kvs = kvs ? 1 : 0;
-  // a pipelined step marks the next batch in the predictor launch, beside its sort block (in the dz0 launch for
-  // graphs marked through summary bitmaps: review-shaped 0.1040 vs 0.1037 ms, not kept)
+  c.kvf = 1;  // (the attention kernels from here on read them)
+  c.kvs = pl.kvs ? 1 : 0;
   probe_begin(TGNX_K_PROJ, s);
-  gemmN_launch(s, gemm_job<G32>(gemm_shape<G32>(kr.Mtr, 4 * HC, D, c.cnt + CNT_M), LoadZ{c.Z0, c.mem, c.nid, D, 0},
-                             LoadProjW{P + c.L.wq, c.L.pw, HC, D}, EpiProj{P + c.L.bq, c.L.pb, c.P, HC}, (float*)nullptr));
+  rc = launch_jobs(L[L_PROJ], s, gemm_job<G32>(shp_proj(kr, c.cnt), LoadZ{c.Z0, c.mem, c.nid, D, 0},
+                                               LoadProjW{P + c.L.wq, c.L.pw, HC, D}, EpiProj{P + c.L.bq, c.L.pb, c.P, HC}, (float*)nullptr));
+  if (rc) return rc;
   probe_end(TGNX_K_PROJ, s);
   TGNX_LAUNCH_CHECK("tgn_proj");
-  // 1 hop: the attention forward runs inside tgn_pred_train (per root, beside its weight staging)
-  const bool att_in_pred = !two;
-  if (!att_in_pred) {
+  if (L[L_ATTN_FWD].issued) {  // (1 hop: the attention forward runs inside tgn_pred_train)
     probe_begin(TGNX_K_SEG_FWD, s);
-    launch_k(tgn_attn_fwd<true>, dim3(gridn(kr.Rtr, 4, 1 << 20)), dim3(256), 0, s, c);
+    launch_p(tgn_attn_fwd<true>, L[L_ATTN_FWD], s, c);
     probe_end(TGNX_K_SEG_FWD, s);
     TGNX_LAUNCH_CHECK("tgn_attn_fwd");
   }
   Ctx cr = two ? root_view(c) : c;  // the level the predictor reads
-  if (two) cr.kvf = cr.kvs = 0;  // conv2's attention backward leaves its (dk, dv) sums to the k / v reduction job
   if (two) {  // conv2 over the roots: projections of h1 (rows = outer centres), attention per root
-    gemm_launch<G32>(gemm_shape<G32>(kr.Rtr, 4 * HC, HC, c.cnt + CNT_R), LoadRowK{c.Zc, kr.Rtr, HC, HC},
-                     LoadProjW{P + c.L.wq2, c.L.pw, HC, HC}, EpiProj{P + c.L.bq2, c.L.pb, c.P2, HC}, nullptr, s);
+    cr.kvf = cr.kvs = 0;  // conv2's attention backward leaves its (dk, dv) sums to the k / v reduction job
+    const GemmShape g2 = shp_proj2(kr, c.cnt);
+    TGNX_CHECK_ARG(gemm_blocks(g2) == L[L_PROJ2].grid, "tgn: conv2's projection does not fill its planned grid");
+    launch_p(gemm_kernel<G32, LoadRowK, LoadProjW, EpiProj>, L[L_PROJ2], s, g2, LoadRowK{c.Zc, kr.Rtr, HC, HC},
+             LoadProjW{P + c.L.wq2, c.L.pw, HC, HC}, EpiProj{P + c.L.bq2, c.L.pb, c.P2, HC}, (float*)nullptr);
     TGNX_LAUNCH_CHECK("tgn_proj2");
-    tgn_attn_fwd<true><<<gridn(kr.R1tr, 4, 1 << 20), 256, 0, s>>>(cr);
+    tgn_attn_fwd<true><<<L[L_ATTN_FWD2].grid, L[L_ATTN_FWD2].block, 0, s>>>(cr);
     TGNX_LAUNCH_CHECK("tgn_attn_fwd2");
   }
-  // where the next batch's scan runs (parity-set steps): all of it as the first workgroups of the dW_cell
-  // launch when its LDS holds the plans; else, for partitioned plans (data parallel: the global batch's
-  // 2 B keys) that fit the predictor launch's LDS, the plans there and the walk alone in the dW_cell launch;
-  // else its own launch after the dW_cell launch
-  // (with a plan table the scan is the walk alone: it rides when the rank's centres fit the launch's LDS, 1 hop in
-  // the attention-backward launch instead of the dW_cell launch)
-  // (with a plan table the scan is the walk alone: its LDS is the centre staging, 3 B x 12 bytes, and the small-graph
-  // direct walk's <= 2 words per thread; 2 hops: the walk rides in conv1's attention-backward launch)
-  // (the attention-backward walk holds 2 bitmap words per thread, the dW_cell launch's ScanJob 8: its LDS word list
-  // takes the 2-hop comment-shaped walk's ~1,100 words; 2 hops: the walk rides there — comment-shaped A/B 0.2383 /
-  // 0.2397 ms against 0.2462 / 0.2459 for the pipelined step, 0.2504 / 0.2498 in the attention backward; the wide
-  // walk in the attention backward cost the wiki step +0.9 %)
-  const auto walk_rides = [&](size_t lds, int wpt) {
-    return (size_t)3 * kr.B * 12 <= lds && (!scan_direct(c.words) || c.words <= (int64_t)wpt * 256);
-  };
-  const bool walk_bwd = ppm && c.ptab && !two && walk_rides((size_t)3 * MARK_LDS_WORDS * 4, 2);
-  const int nwalk = walk_bwd ? 1 : 0;
-  const uint32_t walk_lds = walk_bwd ? (uint32_t)(3 * kr.B * 12 + 16) : 0u;
-  const bool scan_w3 = ppm && !walk_bwd && (c.ptab ? walk_rides((size_t)3 * MARK_LDS_WORDS * 4, 8)
-                                                   : scan_rides(c, k, kr, (size_t)3 * MARK_LDS_WORDS * 4));
-  static const int plans_in_pred = env_int("TGNX_PLANS_IN_PRED", TGNX_PLANS_IN_PRED);  // (runtime A/B switch)
-  const bool plans_pred = ppm && !c.ptab && !scan_w3 && plans_in_pred && c.pplan > 1 && c.pplan <= plans_in_pred &&
-                          2 * k.B <= PRED_PLAN_MAXE * 256 &&
-                          scan_rides(c, kr, kr, (size_t)3 * MARK_LDS_WORDS * 4) &&
-                          tgn_scan_smem(k.B) <= tgn_pred_smem(TDMAX);
-  const int npl = plans_pred ? 2 * c.pplan : 0;
   probe_begin(TGNX_K_PRED, s);
   TGNX_CHECK_ARG(pred_smem_ok(c.D), "tgn_pred_train: dynamic LDS attribute refused");
-  const int nmk = ppm || pipe ? nmark : 0;
-  const size_t psm = std::max({att_in_pred || pred_stages<false>() ? tgn_pred_smem(c.D) : (size_t)16,
-                               nmk ? (size_t)3 * MARK_LDS_WORDS * 4 : (size_t)0,
-                               npl ? tgn_scan_smem(k.B) : (size_t)0});
-  const int nsrt = (two ? cr.kvs : kvs) ? 1 : 0;  // (kvs: the rows fit the sort's LDS counters)
   const PlanOut po = plan_out(ppm ? cn : c);
-  if (att_in_pred)
-    launch_k(c.K <= 10 ? tgn_pred_train<true, 10> : tgn_pred_train<true, ATT_EB>, dim3(kr.B + npl + nsrt + nmk),
-             dim3(64 * pred_waves<true>()), (uint32_t)psm, s, cr, nmk, nsrt, po, npl);
-  else
-    launch_k(tgn_pred_train<false>, dim3((pred_stages<false>() ? pred_groups(kr.B) : kr.B) + npl + nsrt + nmk),
-             dim3(64 * pred_waves<false>()), (uint32_t)psm, s, cr,
-             nmk, nsrt, po, npl);
+  launch_p(L[L_PRED].kernel == TGNX_TGN_PRED_RING10 ? tgn_pred_train<true, 10>
+           : L[L_PRED].kernel == TGNX_TGN_PRED_RING ? tgn_pred_train<true, ATT_EB>
+                                                    : tgn_pred_train<false>,
+           L[L_PRED], s, cr, pl.nmk, pl.nsrt, po, pl.npl);
   probe_end(TGNX_K_PRED, s);
   TGNX_LAUNCH_CHECK("tgn_pred_train");
-  if (c.emb) {
+  if (L[L_EMB_AGG].issued) {
     // DyRepMemory.update_state in train order (memory_module.py:322-325): the memory of src ∪ dst from their
     // stored messages with the embeddings of this batch's forward in place of memory rows (:387-408) — the
     // stores are still the previous batch's (StoreJob runs later); the fixup writes these rows (Zupd)
@@ -5682,172 +5845,150 @@ static int train_step_impl_c(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers*
   if (two) {
     // conv2 backward (‖ predictor reductions) -> dP2, dE2; then dh1 = dP2 [Wq2; Wk2; Wv2; Wsk2] ‖ dW_proj2,
     // dW_edge2 (deferred) ‖ conv2's lin_edge -> Δt-encoding partials; then conv backward from dh1
-    const int ncb1 = gridn(kr.R1tr, 4, 1 << 20);
-    launch_k(attn_bwd_fn(c.K, cr.dzrep, true), dim3(ncb1 + gridn(3 * D + 2, 4)), dim3(256), 0u, s, cr, ncb1, 0, 0, cr);
+    launch_p(attn_bwd_fns[L[L_ATTN_BWD2].kernel], L[L_ATTN_BWD2], s, cr, pl.ncb1, 0, 0, cr);
     TGNX_LAUNCH_CHECK("tgn_attn_bwd2");
     // conv2's (dk, dv) sums ‖ its dE2-only GEMMs (as in the 1-hop step below), then dh1 ‖ dW_proj2
     const auto j_dwe2 = gemm_job<GW>(shp_dWe2(kr, c.cnt), LoadKRow{c.dE2, HC, kr.E1tr, HC}, LoadAttrMapT{ea1},
                                      EpiDeferred{}, c.pF);
-    const auto j_denc2 = gemm_job<G32>(gemm_shape<G32>(kr.E1tr, D, HC, c.cnt + CNT_E1), LoadRowK{c.dE2, kr.E1tr, HC, HC},
+    const auto j_denc2 = gemm_job<G32>(shp_denc2(kr, c.cnt), LoadRowK{c.dE2, kr.E1tr, HC, HC},
                                        LoadKRow{P + c.L.we2, D, HC, D + d},
                                        EpiTeEdge{c.e_j, c.e_t, c.lu, c.tgp, D, c.e1_e2, c.tgp_e1, P + c.L.te_w,
                                                  P + c.L.te_b},
                                        (float*)nullptr);
-    const auto j_dh1 = gemm_job<G32L>(gemm_shape<G32L>(kr.Rtr, HC, 4 * HC, c.cnt + CNT_R),
-                                      LoadRowK{c.dP2, kr.Rtr, 4 * HC, 4 * HC}, LoadProjWT{P + c.L.wq2, c.L.pw, HC, HC},
-                                      EpiStore{c.dZc, nullptr, HC, 0}, (float*)nullptr);
+    const auto j_dh1 = gemm_job<G32L>(shp_dh1(kr, c.cnt), LoadRowK{c.dP2, kr.Rtr, 4 * HC, 4 * HC},
+                                      LoadProjWT{P + c.L.wq2, c.L.pw, HC, HC}, EpiStore{c.dZc, nullptr, HC, 0},
+                                      (float*)nullptr);
     const auto j_dwp2 = gemm_job<GW>(shp_dWp2(kr, c.cnt), LoadKRow{c.dP2, 4 * HC, kr.Rtr, 4 * HC}, LoadZ1T{c.Zc, HC},
                                      EpiDeferred{}, c.pE);
-    gemmN_launch(s, BlockJob<KvReduceJob>{KvReduceJob{cr}, gridn(kr.E1tr, KVR_CH, 1 << 20)}, j_dwe2, j_denc2);
+    if ((rc = launch_jobs(L[L_KV_REDUCE2], s, BlockJob<KvReduceJob>{KvReduceJob{cr}, pl.nkv2}, j_dwe2, j_denc2))) return rc;
     TGNX_LAUNCH_CHECK("tgn_kv_reduce2");
-    gemmN_launch(s, j_dh1, j_dwp2);
+    if ((rc = launch_jobs(L[L_DH1], s, j_dh1, j_dwp2))) return rc;
     TGNX_LAUNCH_CHECK("tgn_dh1");
-    const int ncb = gridn(kr.Rtr, 4, 1 << 20), nkv = kvf ? gridn(kr.Etr, KVE_CH, 1 << 20) : 0;
-    launch_k(attn_bwd_fn(c.K, c.dzrep, true), dim3(ncb + nkv + nwalk), dim3(256), walk_lds, s, c,
-             ncb, nkv, nwalk, nwalk ? cn : c);
-  } else {
-    const int ncb = gridn(kr.Rtr, 4, 1 << 20);
-    const int nkv = kvf ? gridn(kr.Etr, KVE_CH, 1 << 20) : 0;
-    launch_k(attn_bwd_fn(c.K, c.dzrep), dim3(ncb + nkv + gridn(3 * D + 2, 4) + nwalk),
-             dim3(256), walk_lds, s, c, ncb, nkv, nwalk, nwalk ? cn : c);
   }
+  // the centres' attention backward ‖ each edge's (dk, dv) ‖ 1 hop: the predictor reductions (2 hops: they rode in
+  // conv2's) ‖ the next batch's walk (walk_bwd)
+  launch_p(attn_bwd_fns[L[L_ATTN_BWD].kernel], L[L_ATTN_BWD], s, c, pl.ncb, pl.nkv, pl.nwalk, pl.nwalk ? cn : c);
   probe_end(TGNX_K_SEG_BWD, s);
   TGNX_LAUNCH_CHECK("tgn_attn_bwd");
-  // k / v sums into dP ‖ the GEMMs that need only dE: dW_edge (deferred split-K) and dEnc·W_e (Δt
-  // partials of the sampled edges).  Jobs of one gemmN launch add up rather than overlap (measured:
-  // the five backward jobs in one launch took 28 us, dz0 alone 16), while kv_reduce leaves most CUs
-  // idle: the dE-only GEMMs fill them here instead of lengthening the dP launch below.
+  // dz0 = dP W with the memory updater's backward in its epilogue ‖ dW_proj, dW_src/dst (deferred split-K) — all
+  // read only what attn_bwd / pred_train produced; dz0 first in its launch (0.0985 vs 0.0991 ms).  Jobs of one gemmN
+  // launch add up rather than overlap (measured: the five backward jobs in one launch took 28 us, dz0 alone 16).
   const Ctx cf = fixup_view(c);
-  const EpiGradStore e_dWe{G, c.L.we, D + d, cf.adf};
-  const auto j_dwe = gemm_job<GW>(shp_dWe(kr, c.cnt), LoadKRow{c.dE, HC, kr.Etr, HC}, LoadKRow{c.encE, D + d, kr.Etr, D + d},
-                                  EpiDeferred{}, c.pA);
-  const auto j_denc = gemm_job<G32>(with_cap(gemm_shape<G32>(kr.Etr, D, HC, c.cnt + CNT_E), edge_cap), LoadRowK{c.dE, kr.Etr, HC, HC},
-                                    LoadKRow{P + c.L.we, D, HC, D + d}, EpiTeEdge{c.e_j, c.e_t, c.lu, c.tgp, D, nullptr, 0, P + c.L.te_w, P + c.L.te_b},
+  const auto j_dz0 = gemm_job<G32L>(shp_dz0(kr, c.cnt, pl.md_cap), LoadRowK{c.dP, kr.Mtr, 4 * HC, 4 * HC},
+                                    LoadProjWT{P + c.L.wq, c.L.pw, HC, D}, Cl::bwd(c), (float*)nullptr);
+  const auto j_dwp = gemm_job<GW>(shp_dWp(kr, c.cnt), LoadKRow{c.dP, 4 * HC, kr.Mtr, 4 * HC}, LoadZ1T{c.Z0, D},
+                                  EpiDeferred{}, c.pB);
+  const auto j_dwlp = gemm_job<GW>(shp_dWlp(kr, c.cnt), LoadLpA{c.evs, c.ctl, D, evs_stride(D)},
+                                   LoadLpB{c.evs, c.ctl, D, evs_stride(D)}, EpiDeferred{}, c.pC);
+  // parity sets: the next batch's scan (into set 1 - parity; the counters advance in the fixup launch)
+  const auto j_scan = BlockJob<ScanJob, 3 * MARK_LDS_WORDS>{ScanJob{cn}, pl.nscanj};
+  probe_begin(TGNX_K_EDGE_BWD, s);
+  if (L[L_WGRAD_DZ0].kernel)  // (carries the ScanJob: TGNX_SCAN_AT 6)
+    rc = launch_jobs(L[L_WGRAD_DZ0], s, j_scan, j_dz0, j_dwp, j_dwlp);
+  else  // (dW_edge in this launch: slower, r4_dwe_in_dz0_ab.txt)
+    rc = launch_jobs(L[L_WGRAD_DZ0], s, j_dz0, j_dwp, j_dwlp);
+  if (rc) return rc;
+  probe_end(TGNX_K_EDGE_BWD, s);
+  TGNX_LAUNCH_CHECK("tgn_wgrad_dz0");
+  // dW_cell, dX_enc (Δt partials of the messages) ‖ the GEMMs that need only dE: dW_edge (deferred split-K) and
+  // dEnc·W_e (Δt partials of the sampled edges) — in the dz0 launch: 0.1013 vs 0.0987 ms; dW_proj / dW_lp moved here
+  // too: 0.1013 - 0.1035 — ‖ the fixup's descriptor copy + the counter advance (SnapJob) ‖ the message stores.  The
+  // GEMM jobs before the snapshot / store blocks (0.0970 vs 0.0986 ms with those first); the edge jobs dEnc / dW_edge
+  // first instead: that launch 12.8 -> 14.7 us, r5_w3_jobs_first_ab.txt
+  const int rows_edge = (kr.Etr + G32::TM - 1) / G32::TM, rows_msg = (kr.Mtr + G32::TM - 1) / G32::TM;
+  const auto j_dxe = gemm_job<GXE>(shp_dxe(kr, c.cnt, pl.md_cap), LoadRowK{c.dG, kr.Mtr, Cl::G * D, Cl::G * D},
+                                   Cl::wenc(c), EpiTeMsg{c.s0m, c.s1m, c.tgp, D, rows_edge}, (float*)nullptr);
+  const auto j_dwg = gemm_job<GW>(shp_dWg(kr, c.cnt), LoadKRow{c.dG, Cl::G * D, kr.Mtr, Cl::G * D}, Cl::hT(c),
+                                  EpiDeferred{}, c.pD);
+  const auto j_dwe = gemm_job<GW>(shp_dWe(kr, c.cnt), LoadKRow{c.dE, HC, kr.Etr, HC},
+                                  LoadKRow{c.encE, D + d, kr.Etr, D + d}, EpiDeferred{}, c.pA);
+  const auto j_denc = gemm_job<G32>(shp_denc(kr, c.cnt, pl.edge_cap), LoadRowK{c.dE, kr.Etr, HC, HC},
+                                    LoadKRow{P + c.L.we, D, HC, D + d},
+                                    EpiTeEdge{c.e_j, c.e_t, c.lu, c.tgp, D, nullptr, 0, P + c.L.te_w, P + c.L.te_b},
                                     (float*)nullptr);
-  // weight gradients (deferred split-K) ‖ ...
+  const auto j_snap = BlockJob<SnapJob>{SnapJob{c, ppm ? 1 : 0}, 1};
+  const auto j_store = BlockJob<StoreJob>{StoreJob{c, pl.nst, pl.nmem7}, pl.nst + pl.nmem7};
+  probe_begin(TGNX_K_WGRAD3, s);
+  if (L[L_WGRAD3].kernel)  // (carries the ScanJob)
+    rc = launch_jobs(L[L_WGRAD3], s, j_scan, j_dxe, j_dwg, j_dwe, j_denc, j_snap, j_store);
+  else
+    rc = launch_jobs<TGNX_W3_WAVES>(L[L_WGRAD3], s, j_dxe, j_dwg, j_dwe, j_denc, j_snap, j_store);
+  if (rc) return rc;
+  probe_end(TGNX_K_WGRAD3, s);
+  TGNX_LAUNCH_CHECK("tgn_wgrad3");
+  if (L[L_SCAN_EARLY].issued) {  // (with a plan table: the walk alone)
+    tgn_scan<true><<<L[L_SCAN_EARLY].grid, L[L_SCAN_EARLY].block, L[L_SCAN_EARLY].lds, s>>>(cn, 1, 0);
+    TGNX_LAUNCH_CHECK("tgn_scan_early");
+  }
+  // split-K sums + epilogues (weight gradients, Adam) ‖ Δt reduction ‖ update_state's memory half (train order:
+  // memory of src ∪ dst from this step's GRU rows; the stores and the ring insert ran in earlier launches), reading
+  // the step descriptor from SnapJob's copy (cf); its head blocks: the next batch's scan (fold) or gather
+  const EpiGradStore e_dWe{G, c.L.we, D + d, cf.adf};
   const EpiProjGrad e_dWp{G, c.L.wq, c.L.bq, c.L.pw, c.L.pb, HC, D, cf.adf};
   const EpiLpGrad e_dWlp{G, c.L.lsw, c.L.ldw, D, cf.adf};
   const auto e_dWg = Cl::wgrad(cf);
-  // one launch: dW_proj, dW_src/dst (deferred split-K) ‖ dz0 = dP W with the GRU backward in its
-  // epilogue — all read only what attn_bwd / kv_reduce / pred_train produced
-  const int rows_edge = (kr.Etr + G32::TM - 1) / G32::TM, rows_msg = (kr.Mtr + G32::TM - 1) / G32::TM;
-  probe_begin(TGNX_K_EDGE_BWD, s);
-  const auto j_dwp = gemm_job<GW>(shp_dWp(kr, c.cnt), LoadKRow{c.dP, 4 * HC, kr.Mtr, 4 * HC}, LoadZ1T{c.Z0, D}, EpiDeferred{}, c.pB);
-  const auto j_dwlp = gemm_job<GW>(shp_dWlp(kr, c.cnt), LoadLpA{c.evs, c.ctl, D, evs_stride(D)},
-                                   LoadLpB{c.evs, c.ctl, D, evs_stride(D)}, EpiDeferred{}, c.pC);
-  const auto j_dz0 = gemm_job<G32L>(with_cap(gemm_shape<G32L>(kr.Mtr, D, 4 * HC, c.cnt + CNT_M), md_cap), LoadRowK{c.dP, kr.Mtr, 4 * HC, 4 * HC},
-                                    LoadProjWT{P + c.L.wq, c.L.pw, HC, D}, Cl::bwd(c), (float*)nullptr);
-  auto l7 = [&](auto... jobs) {
-    gemmN_launch(s, jobs...);
-    probe_end(TGNX_K_EDGE_BWD, s);
-    TGNX_LAUNCH_CHECK("tgn_wgrad_dz0");
-    return TGNX_OK;
+  const TeReduceTail te{cf, rows_edge, rows_msg};
+  const auto fixup = [&](const auto& tail, int head, const auto&... more) {
+    return launch_fixup(L[L_FIXUP], pl.nfix, s, tail, head, gemm_fix<GW>(shp_dWe(kr, cf.cnt), c.pA, e_dWe),
+                        gemm_fix<GW>(shp_dWp(kr, cf.cnt), c.pB, e_dWp), gemm_fix<GW>(shp_dWlp(kr, cf.cnt), c.pC, e_dWlp),
+                        gemm_fix<GW>(shp_dWg(kr, cf.cnt), c.pD, e_dWg), more...);
   };
-  // ‖ the message stores ‖ the fixup's descriptor copy + the counter advance (SnapJob)
-  const int nst = gridn(2 * k.B, 256);
-  const auto j_dwg = gemm_job<GW>(shp_dWg(kr, c.cnt), LoadKRow{c.dG, Cl::G * D, kr.Mtr, Cl::G * D},
-                                  Cl::hT(c), EpiDeferred{}, c.pD);
-  const auto j_dxe = gemm_job<GXE>(with_cap(gemm_shape<GXE>(kr.Mtr, D, Cl::G * D, c.cnt + CNT_M), md_cap),
-                                    LoadRowK{c.dG, kr.Mtr, Cl::G * D, Cl::G * D}, Cl::wenc(c),
-                                    EpiTeMsg{c.s0m, c.s1m, c.tgp, D, rows_edge}, (float*)nullptr);
-  // ppm: the next batch's scan (into set 1 - pp; the counters advance in the fixup launch) as this launch's
-  // first workgroups when it fits their LDS, else its own launch after it
-  const auto j_scan = BlockJob<ScanJob, 3 * MARK_LDS_WORDS>{ScanJob{cn}, walk_bwd ? 0 : plans_pred || c.ptab ? 1 : 1 + 2 * c.pplan};
-  const auto j_snap = BlockJob<SnapJob>{SnapJob{c, ppm ? 1 : 0}, 1};
-  const int nmem = gridn(kr.Ucap, 4, 1024);
-  const int nmem7 = ga ? nmem : 0;  // (gather-ahead: the memory / last_update half rides here, not in the fixup)
-  const auto j_store = BlockJob<StoreJob>{StoreJob{c, nst, nmem7}, nst + nmem7};
-  // (the scan may ride in the dz0 launch instead: TGNX_SCAN_AT 6)
-  const bool scan6 = scan_w3 && TGNX_SCAN_AT == 6;
-  const bool walk_w3 = (scan_w3 || plans_pred) && !walk_bwd;  // (the walk rides in the dW_cell launch)
-  auto l8 = [&](auto... jobs) {
-    probe_begin(TGNX_K_WGRAD3, s);
-    // the GEMM jobs before the snapshot / store blocks (0.0970 vs 0.0986 ms with those first)
-    // (the edge jobs dEnc / dW_edge first instead: that launch 12.8 -> 14.7 us, r5_w3_jobs_first_ab.txt)
-    if (walk_w3 && !scan6)
-      gemmN_launch(s, j_scan, j_dxe, j_dwg, jobs..., j_snap, j_store);
-    else
-      gemmN_launch_w<TGNX_W3_WAVES>(s, j_dxe, j_dwg, jobs..., j_snap, j_store);
-    probe_end(TGNX_K_WGRAD3, s);
-    TGNX_LAUNCH_CHECK("tgn_wgrad3");
-    return TGNX_OK;
-  };
-  // kvf: the dE-only GEMMs ride in the dW_gru launch (in the dz0 launch: 0.1013 vs 0.0987 ms; dW_proj / dW_lp
-  // moved to the dW_gru launch too: 0.1013 - 0.1035), dz0 first in its launch (0.0985 vs 0.0991)
-  // (the lambdas return the launch checks' status)
-  if (scan6) {
-    if ((rc = l7(j_scan, j_dz0, j_dwp, j_dwlp)) || (rc = l8(j_dwe, j_denc))) return rc;
-  } else if ((rc = l7(j_dz0, j_dwp, j_dwlp)) || (rc = l8(j_dwe, j_denc))) {  // (dW_edge in the dz0 launch: slower,
-    return rc;                                                                 //  r4_dwe_in_dz0_ab.txt)
-  }
-  if (ppm && !walk_w3 && !walk_bwd) {  // (with a plan table: the walk alone)
-    tgn_scan<true><<<c.ptab ? 1 : 1 + 2 * c.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B), s>>>(cn, 1, 0);
-    TGNX_LAUNCH_CHECK("tgn_scan_early");
-  }
-  // split-K sums + epilogues ‖ Δt reduction ‖ update_state's memory half (train order: memory of src ∪
-  // dst from this step's GRU rows; the stores and the ring insert ran in earlier launches), reading the
-  // step descriptor from SnapJob's copy (cf) — so that the pipelined step's next-batch scan (counters
-  // advanced by SnapJob) rides in the same launch as its first workgroups when it fits (scan_folds)
-  const int nte = (2 * D + 63) / 64;
-  const bool scan_next = pipe && !no_tail && !ppm;
-  const bool fold = scan_next && scan_folds(c, k, kr);
-  const int nscan = fold ? 1 + 2 * c.pplan : 0;
-  const TrainTail<false> tail{TeReduceTail{cf, rows_edge, rows_msg}, c, nscan, nte, nmem, ppm ? 1 : 0, gat, 0};
+  const TrainTail<false> tail{te, c, pl.nscan, pl.nte, pl.nmem, ppm ? 1 : 0, gat, 0};
   probe_begin(TGNX_K_FINISH, s);
-  if (ga) {  // the next batch's gather first in the launch, on the other parity's set
-    const TrainTail<true> tga{TeReduceTail{cf, rows_edge, rows_msg}, cn, 0, nte, 0, 1, gat, ngat};
-    gemm_fixup_launch_h(TGNX_GA_FIRST ? ngat : 0, ngat + nte, tga, s, gemm_fix<GW>(shp_dWe(kr, cf.cnt), c.pA, e_dWe),
-                        gemm_fix<GW>(shp_dWp(kr, cf.cnt), c.pB, e_dWp), gemm_fix<GW>(shp_dWlp(kr, cf.cnt), c.pC, e_dWlp),
-                        gemm_fix<GW>(shp_dWg(kr, cf.cnt), c.pD, e_dWg));
-  } else if (two)
-    gemm_fixup_launch_h(nscan, nscan + nte + nmem, tail, s, gemm_fix<GW>(shp_dWe(kr, cf.cnt), c.pA, e_dWe),
-                        gemm_fix<GW>(shp_dWp(kr, cf.cnt), c.pB, e_dWp), gemm_fix<GW>(shp_dWlp(kr, cf.cnt), c.pC, e_dWlp),
-                        gemm_fix<GW>(shp_dWg(kr, cf.cnt), c.pD, e_dWg),
-                        gemm_fix<GW>(shp_dWp2(kr, cf.cnt), c.pE, EpiProjGrad{G, c.L.wq2, c.L.bq2, c.L.pw, c.L.pb, HC, HC, cf.adf}),
-                        gemm_fix<GW>(shp_dWe2(kr, cf.cnt), c.pF, EpiGradStore{G, c.L.we2, D + d, cf.adf}));
+  if (L[L_FIXUP].kernel == TGNX_TGN_FIXUP_GATHER)  // the next batch's gather first in the launch, on the other parity's set
+    rc = fixup(TrainTail<true>{te, cn, 0, pl.nte, 0, 1, gat, pl.ngat}, TGNX_GA_FIRST ? pl.ngat : 0);
+  else if (L[L_FIXUP].kernel == TGNX_TGN_FIXUP_2HOP)
+    rc = fixup(tail, pl.nscan,
+               gemm_fix<GW>(shp_dWp2(kr, cf.cnt), c.pE, EpiProjGrad{G, c.L.wq2, c.L.bq2, c.L.pw, c.L.pb, HC, HC, cf.adf}),
+               gemm_fix<GW>(shp_dWe2(kr, cf.cnt), c.pF, EpiGradStore{G, c.L.we2, D + d, cf.adf}));
   else
-    gemm_fixup_launch_h(nscan, nscan + nte + nmem, tail, s, gemm_fix<GW>(shp_dWe(kr, cf.cnt), c.pA, e_dWe),
-                        gemm_fix<GW>(shp_dWp(kr, cf.cnt), c.pB, e_dWp), gemm_fix<GW>(shp_dWlp(kr, cf.cnt), c.pC, e_dWlp),
-                        gemm_fix<GW>(shp_dWg(kr, cf.cnt), c.pD, e_dWg));
+    rc = fixup(tail, pl.nscan);
+  if (rc) return rc;
   probe_end(TGNX_K_FINISH, s);
   TGNX_LAUNCH_CHECK("tgn_fixup_update");
-  if (scan_next && !fold) {  // the next batch (counters advanced by SnapJob): sorted node sets, plans, descriptor
-    train_scan(s, c, k);
+  if (L[L_SCAN_NEXT].issued) {  // the next batch (counters advanced by SnapJob): sorted node sets, plans, descriptor
+    train_scan(s, c, L[L_SCAN_NEXT]);
     TGNX_LAUNCH_CHECK("tgn_scan_next");
   }
   return TGNX_OK;
 }
-
 }  // extern "C++"
 
 static int train_step_impl(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t gen_neg, int32_t dropout,
-                           void* stream, bool fuse_adam, const Cursor* adv = nullptr, int pipe = 0, int pp = -1) {
-  if (cfg && cfg->updater == 1) return train_step_impl_c<1>(cfg, buf, gen_neg, dropout, stream, fuse_adam, adv, pipe, pp);
-  return train_step_impl_c<0>(cfg, buf, gen_neg, dropout, stream, fuse_adam, adv, pipe, pp);
+                           void* stream, const StepMode& m) {
+  if (cfg && cfg->updater == 1) return train_step_impl_c<1>(cfg, buf, gen_neg, dropout, stream, m);
+  return train_step_impl_c<0>(cfg, buf, gen_neg, dropout, stream, m);
 }
-
+static Prefetch prefetch_of(int32_t prefetched) { return prefetched ? Prefetch::Prepared : Prefetch::PrepareFirst; }
 int tgnx_tgn_train_fwd_bwd(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t gen_neg, int32_t dropout,
                            void* stream) {
-  return train_step_impl(cfg, buf, gen_neg, dropout, stream, false);
+  StepMode m;
+  return train_step_impl(cfg, buf, gen_neg, dropout, stream, m);
 }
 
 int tgnx_tgn_train_step(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int32_t gen_neg, int32_t dropout,
                         void* stream) {
-  return train_step_impl(cfg, buf, gen_neg, dropout, stream, true);
+  StepMode m;
+  m.fuse_adam = true;
+  return train_step_impl(cfg, buf, gen_neg, dropout, stream, m);
 }
 
 int tgnx_tgn_train_step_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                  int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                  int32_t dropout, void* stream) {
   const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
-  return train_step_impl(cfg, buf, 1, dropout, stream, true, &a);
+  StepMode m;
+  m.fuse_adam = true; m.cursor = &a;
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
 int tgnx_tgn_train_step_pipelined(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                   int64_t split_hi, int64_t batch, uint64_t base_seed, int32_t dropout,
                                   int32_t prefetched, void* stream) {
   const Cursor a{split_lo, split_hi, batch, 0, 1, base_seed};
-  return train_step_impl(cfg, buf, 1, dropout, stream, true, &a, prefetched ? 1 : 2);
+  StepMode m;
+  m.fuse_adam = true; m.cursor = &a; m.prefetch = prefetch_of(prefetched);
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
 int tgnx_tgn_train_step_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo, int64_t split_hi,
@@ -5855,7 +5996,9 @@ int tgnx_tgn_train_step_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* b
                            void* stream) {
   const Cursor a{split_lo, split_hi, batch, 0, 1, base_seed};
   TGNX_CHECK_ARG(parity == 0 || parity == 1, "tgnx_tgn_train_step_pp: parity must be 0 or 1");
-  return train_step_impl(cfg, buf, 1, dropout, stream, true, &a, prefetched ? 1 : 2, parity);
+  StepMode m;
+  m.fuse_adam = true; m.cursor = &a; m.prefetch = prefetch_of(prefetched); m.parity = parity;
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
 int tgnx_tgn_train_fwd_bwd_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
@@ -5869,20 +6012,24 @@ int tgnx_tgn_train_fwd_bwd_pp(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers
     if (rc) return rc;
   }
   const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
-  return train_step_impl(cfg, buf, 1, dropout, stream, false, &a, prefetched ? 1 : 2, parity);
+  StepMode m;
+  m.cursor = &a; m.prefetch = prefetch_of(prefetched); m.parity = parity;
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
 int tgnx_tgn_train_fwd_bwd_split(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                  int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                  int32_t dropout, int32_t prefetched, void* stream) {
   const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
-  return train_step_impl(cfg, buf, 1, dropout, stream, false, &a, (prefetched ? 1 : 2) | 4);
+  StepMode m;
+  m.cursor = &a; m.prefetch = prefetch_of(prefetched); m.caller_scans = true;
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
-// the train step's scan of a batch (sorted node sets, plans, descriptor); the caller checks the launch under its label
-static void train_scan(hipStream_t s, const Ctx& c, const Caps& k) {
+// a whole scan as its own launch (the train step's, tgnx_tgn_scan_next); the caller checks the launch under its label
+static void train_scan(hipStream_t s, const Ctx& c, const tgnx_tgn_launch& l) {
   probe_begin(TGNX_K_ASSEMBLE, s);
-  tgn_scan<true><<<1 + 2 * c.pplan, TGNX_SCAN_T, tgn_scan_smem(k.B), s>>>(c, 0, 1);
+  tgn_scan<true><<<l.grid, l.block, l.lds, s>>>(c, 0, 1);
   probe_end(TGNX_K_ASSEMBLE, s);
 }
 int tgnx_tgn_scan_next(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo, int64_t split_hi,
@@ -5895,8 +6042,28 @@ int tgnx_tgn_scan_next(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, 
   const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
   TGNX_CHECK_ARG(cursor_ok(a, cfg, c), "tgnx_tgn_scan_next: bad cursor arguments");
   set_cursor(c, a);
-  train_scan(as_stream(stream), c, k);
+  train_scan(as_stream(stream), c, scan_launch(L_SCAN_NEXT, c.pplan, k.B));
   TGNX_LAUNCH_CHECK("tgn_scan_next");
+  return TGNX_OK;
+}
+
+int tgnx_tgn_step_plan(const tgnx_tgn_config* cfg, int32_t fuse_adam, int32_t world, int32_t prefetch,
+                       int32_t caller_scans, int32_t parity, int32_t xrows, int32_t plan_table, int32_t flags,
+                       tgnx_tgn_launch* out) {
+  int rc = check_cfg(cfg);
+  if (rc) return rc;
+  TGNX_CHECK_ARG(out && world >= 0 && prefetch >= TGNX_TGN_PREFETCH_PLAIN && prefetch <= TGNX_TGN_PREFETCH_FIRST &&
+                     parity >= -1 && parity <= 1,
+                 "tgnx_tgn_step_plan: bad arguments");
+  const Cursor a{0, 0, 0, 0, world, 0};
+  StepMode m;
+  m.fuse_adam = fuse_adam != 0; m.cursor = world ? &a : nullptr; m.caller_scans = caller_scans != 0; m.parity = parity;
+  m.prefetch = prefetch == TGNX_TGN_PREFETCH_PREPARED ? Prefetch::Prepared
+               : prefetch == TGNX_TGN_PREFETCH_FIRST  ? Prefetch::PrepareFirst
+                                                      : Prefetch::Plain;
+  const StepPlan pl = plan_step(make_caps(cfg), rank_caps(cfg, world ? world : 1), m,
+                                step_facts(cfg, xrows != 0, plan_table != 0, flags));
+  std::copy(pl.L, pl.L + L_COUNT, out);
   return TGNX_OK;
 }
 
@@ -5904,14 +6071,18 @@ int tgnx_tgn_train_fwd_bwd_pipelined(const tgnx_tgn_config* cfg, const tgnx_tgn_
                                      int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                      int32_t dropout, int32_t prefetched, void* stream) {
   const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
-  return train_step_impl(cfg, buf, 1, dropout, stream, false, &a, prefetched ? 1 : 2);
+  StepMode m;
+  m.cursor = &a; m.prefetch = prefetch_of(prefetched);
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
 int tgnx_tgn_train_fwd_bwd_resident(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, int64_t split_lo,
                                     int64_t split_hi, int64_t batch, int32_t rank, int32_t world, uint64_t base_seed,
                                     int32_t dropout, void* stream) {
   const Cursor a{split_lo, split_hi, batch, rank, world, base_seed};
-  return train_step_impl(cfg, buf, 1, dropout, stream, false, &a);
+  StepMode m;
+  m.cursor = &a;
+  return train_step_impl(cfg, buf, 1, dropout, stream, m);
 }
 
 int tgnx_tgn_apply_rows(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, float* rows, int64_t nrows,

@@ -56,6 +56,7 @@ SIGNATURES = {
     "tgnx_tgn_train_fwd_bwd_pp": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_u64, c_i32, c_i32, c_i32,
                                                   c_i32, P, c_i64, c_vp]),
     "tgnx_tgn_scan_next": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_u64, c_vp]),
+    "tgnx_tgn_step_plan": (ctypes.c_int, [P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     "tgnx_tgn_eval_step": (ctypes.c_int, [P, P, c_i32, c_vp]),
     "tgnx_tgn_eval_step_resident": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_u64, P, c_vp]),
     "tgnx_tgn_embed_max_nodes": (c_i64, [P]),
@@ -151,6 +152,16 @@ SIGNATURES = {
     "tgnx_gemm_probe_batch_ws_bytes": (c_sz, [P]),
     "tgnx_gemm_probe_batch": (ctypes.c_int, [P, c_i32, P, c_i32, c_i32, P, P, P, c_sz, c_vp]),
 }
+# a train step's launches in order (TGNX_TGN_STEP_LABELS of include/tgnx.h): tgnx_tgn_step_plan's records
+STEP_LABELS = ("tgn_mark", "tgn_scan", "tgn_gather", "tgn_agg_emit", "tgn_gru_edge", "tgn_proj", "tgn_attn_fwd", "tgn_proj2",
+               "tgn_attn_fwd2", "tgn_pred_train", "tgn_emb_update", "tgn_emb_update_gru", "tgn_attn_bwd2", "tgn_kv_reduce2",
+               "tgn_dh1", "tgn_attn_bwd", "tgn_wgrad_dz0", "tgn_wgrad3", "tgn_scan_early", "tgn_fixup_update", "tgn_scan_next")
+
+
+class TgnLaunch(ctypes.Structure):                                      # tgnx_tgn_launch
+    _fields_ = [(n, c_i32) for n in ("label", "issued", "grid", "block", "lds", "kernel")]
+
+
 GEMM_PROBE_CFGS = {"G32": 0, "G32L": 1, "GW": 2, "G64": 3, "GD": 4}    # TGNX_GEMM_PROBE_* of include/tgnx.h
 
 

@@ -1923,31 +1923,33 @@ class TgnEngine:
     def _dp_pp(self) -> bool:
         return self.dp and self._pp()
 
+    # the resident step's entry point, keyed as the library's StepMode names the mode: (parity sets, pipelined, Adam
+    # fused, the caller scans the next batch) -> (symbol, whether it takes rank / world: the world-1-only forms do not)
+    _ENTRY = {(True, True, False, False): ("tgnx_tgn_train_fwd_bwd_pp", True),
+              (True, True, True, False): ("tgnx_tgn_train_step_pp", False),
+              (False, True, True, False): ("tgnx_tgn_train_step_pipelined", False),
+              (False, True, False, True): ("tgnx_tgn_train_fwd_bwd_split", True),
+              (False, True, False, False): ("tgnx_tgn_train_fwd_bwd_pipelined", True),
+              (False, False, True, False): ("tgnx_tgn_train_step_resident", True),
+              (False, False, False, False): ("tgnx_tgn_train_fwd_bwd_resident", True)}
+
     def _pre(self, prefetched: bool = False, parity=None, apply=None):
         self._emb_all = True
         adv, fb = self._f[:2]
         lo, hi, batch = self._res
         st = self._stream()
-        par = self._parity if parity is None else parity
-        if self._dp_pp():
-            ap = self._apply_pending if apply is None else apply
-            rc = _lib.lib().tgnx_tgn_train_fwd_bwd_pp(self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world,
-                                                     self.seed, self._res_drop, 1 if prefetched else 0, par,
-                                                     1 if ap else 0, ctypes.c_void_p(self.xgather.data_ptr()),
-                                                     ctypes.c_int64(self.xgather.shape[0]), st)
-        elif self._pp():
-            rc = _lib.lib().tgnx_tgn_train_step_pp(self._cfg_ref, self._buf_ref, lo, hi, batch, self.seed, self._res_drop,
-                                                  1 if prefetched else 0, par, st)
-        elif self._pipelined() and self._res_fused:
-            rc = _lib.lib().tgnx_tgn_train_step_pipelined(self._cfg_ref, self._buf_ref, lo, hi, batch, self.seed,
-                                                         self._res_drop, 1 if prefetched else 0, st)
-        elif self._pipelined():
-            f = _lib.lib().tgnx_tgn_train_fwd_bwd_split if self._split() else _lib.lib().tgnx_tgn_train_fwd_bwd_pipelined
-            rc = f(self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world, self.seed, self._res_drop,
-                   1 if prefetched else 0, st)
-        elif self.fold_cursor:   # the batch cursor folded into the step's first launches
-            f = _lib.lib().tgnx_tgn_train_step_resident if self._res_fused else _lib.lib().tgnx_tgn_train_fwd_bwd_resident
-            rc = f(self._cfg_ref, self._buf_ref, lo, hi, batch, self.dp_rank, self.world, self.seed, self._res_drop, st)
+        if self.fold_cursor:   # the batch cursor folded into the step's first launches
+            pp, pipelined = self._pp(), self._pipelined()
+            name, ranked = self._ENTRY[pp, pipelined, bool(self._res_fused), self._split()]
+            args = [lo, hi, batch] + ([self.dp_rank, self.world] if ranked else []) + [self.seed, self._res_drop]
+            if pipelined:
+                args.append(1 if prefetched else 0)
+            if pp:
+                args.append(self._parity if parity is None else parity)
+            if self._dp_pp():   # the previous step's exchanged rows + Adam at the head of this one
+                ap = self._apply_pending if apply is None else apply
+                args += [1 if ap else 0, ctypes.c_void_p(self.xgather.data_ptr()), ctypes.c_int64(self.xgather.shape[0])]
+            rc = getattr(_lib.lib(), name)(self._cfg_ref, self._buf_ref, *args, st)
         else:
             rc = adv(self._ctl_p, 1, 0, 0, 0, lo, hi, batch, self.dp_rank, self.world, self.seed, 1, st)
             rc |= fb(self._cfg_ref, self._buf_ref, 1, self._res_drop, st)
