@@ -288,6 +288,45 @@ int tgnx_tcsr_sample(const int64_t* indptr, const int64_t* indices, const int64_
                      int64_t cut_eid_all, const float* cut_t, int64_t* out_nbr, int64_t* out_eid, float* out_t,
                      int32_t* out_cnt, void* stream);
 
+/* ---------------------------------------------------------------- pair index and hist_rnd evaluation negatives
+ * TGB's link-prediction protocol ranks each positive against `hist_rnd` negatives: destinations the source met
+ * before (and is not meeting now) and random destinations that are neither.  TGB generates them offline on the
+ * CPU; here they come from a device index of the stream's (source, destination) pairs (DESIGN §3b-12 has the
+ * contract, tests/tgb_negs_ref.py restates it).
+ *
+ * Pair index over rows [0, num_rows) of (src, dst): indptr int64[N+1], indices int64[nnz] (each source's distinct
+ * destinations, ascending), first int64[nnz] (the first row at which the pair occurred).  indices / first hold
+ * num_rows entries (nnz <= num_rows); *nnz (host, may be NULL) receives nnz = indptr[N] after one synchronisation
+ * (offline preprocessing, as tgnx_tcsr_build's *chrono).  Sources must lie in [0, num_nodes), destinations in
+ * [0, 2^32), num_nodes <= 2^32, num_rows < 2^31 - 1: TGNX_EINVAL otherwise. */
+size_t tgnx_pair_index_build_ws_bytes(int64_t num_rows);
+int tgnx_pair_index_build(const int64_t* src, const int64_t* dst, int64_t num_rows, int64_t num_nodes, int64_t* indptr,
+                          int64_t* indices, int64_t* first, int64_t* nnz, void* ws, size_t ws_bytes, void* stream);
+/* out[i] (one byte, 0 / 1) = the pair (src[i], dst[i]) occurred at a row < before[i] (before_all when before is
+ * NULL).  A source outside [0, num_nodes) has seen nothing. */
+int tgnx_pair_index_contains(const int64_t* indptr, const int64_t* indices, const int64_t* first, int64_t num_nodes,
+                             const int64_t* src, const int64_t* dst, int64_t n, const int64_t* before,
+                             int64_t before_all, uint8_t* out, void* stream);
+/* k negatives for each event row e of [lo, hi) of a chronological table (t non-decreasing over [lo, hi); t is
+ * double[num_events] when t_f64, else float[num_events], and is compared in that type):
+ *   P = destinations of the rows of [lo, hi) with e's source and timestamp; Hc = the source's index row restricted
+ *   to first < hist_hi; Hn = Hc \ P; X = Hc ∪ P; valid = pool \ X (pool: sorted unique ids below 2^32);
+ *   columns [0, k_hist[r]): min(q, |Hn|) historical picks, ascending — all of Hn, or the first q distinct values
+ *   outside P of Hc[((hash4(seed, 0x68697374, e, a) >> 11) * |Hc|) >> 53], a = 0, 1, ...;
+ *   columns [k_hist[r], k): random picks, ascending — the first distinct values outside X of
+ *   pool[((hash4(seed, 0x726E6473, e, a) >> 11) * |pool|) >> 53]; valid[i mod |valid|] when valid is too small;
+ *   -1 when it is empty.
+ * A draw loop makes at most max_draws draws (0: 16 * its target + 256) and is then filled up with the smallest ids
+ * not yet taken.  status int64[4] (device): the first output row with an empty valid set (-1: none), the rows
+ * whose historical / random part was filled up, the rows filled cyclically.  k <= 1024 and 0 <= q <= k, else
+ * TGNX_EINVAL before any launch.  The result does not depend on the launch geometry. */
+size_t tgnx_negs_hist_rnd_ws_bytes(int64_t nnz, int64_t num_rows);
+int tgnx_negs_hist_rnd(const int64_t* src, const int64_t* dst, const void* t, int32_t t_f64, int64_t num_events,
+                       int64_t lo, int64_t hi, int32_t k, int32_t q, int64_t hist_hi, const int64_t* indptr,
+                       const int64_t* indices, const int64_t* first, int64_t num_nodes, int64_t nnz,
+                       const int64_t* pool, int64_t n_pool, uint64_t seed, int64_t max_draws, int64_t* out,
+                       int32_t* k_hist, int64_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- TGN memory path
  * SURVEY §8 a14–a16 (the PyG TGN of the reference modules/ directory, wired as pyg_model_utils.py:10-36):
  * TGNMemory (modules/memory_module.py:25-215) with IdentityMessage (msg_func.py:12-18) and

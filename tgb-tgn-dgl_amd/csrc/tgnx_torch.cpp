@@ -11,6 +11,9 @@
 //   neg_sample                               NegLinkSamplerDest.sample (neg_sampler.py:8-23)
 //   block_ids                                get_block / dependecyAwareBatch (dependencyGraph.py:8-49), CPU
 //   tcsr_build / tcsr_sample                 TGL's ext_full.npz + recent sampler (utils.py:73, README.md:2-5)
+//   pair_index_build / pair_index_contains / negs_hist_rnd
+//                                            the (source, destination) pair index and TGB's hist_rnd evaluation
+//                                            negatives drawn from it (csrc/tgnx_negs.hip; tgnx/tgb_negs.py)
 //   gemm_f32                                 the modules' Linear contractions on the MFMA GEMM
 //   msg_agg_last / msg_agg_mean              LastAggregator / MeanAggregator (modules/msg_agg.py:15-26)
 //   gru_update                               TGNMemory.memory_updater GRUCell / RNNCell (memory_module.py:70-78)
@@ -196,6 +199,90 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> tcsr_sample(const at:
                             ot.data_ptr<float>(), cnt.data_ptr<int32_t>(), cur_stream()),
            "tgnx_tcsr_sample");
   return {nbr, oe, ot, cnt};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pair_index_build(const at::Tensor& src, const at::Tensor& dst,
+                                                                int64_t num_nodes) {
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(dst, at::kLong, "dst");
+  same_device(src, {&dst});
+  TORCH_CHECK(dst.numel() == src.numel(), "src and dst must have the same length");
+  const c10::OptionalDeviceGuard guard(src.device());
+  const int64_t n = src.numel();
+  auto lopt = src.options();
+  at::Tensor indptr = at::empty({num_nodes + 1}, lopt), indices = at::empty({std::max<int64_t>(n, 1)}, lopt);
+  at::Tensor first = at::empty({std::max<int64_t>(n, 1)}, lopt);
+  const size_t nb = tgnx_pair_index_build_ws_bytes(n);
+  at::Tensor ws = at::empty({(int64_t)std::max<size_t>(nb, 1)}, lopt.dtype(at::kByte));
+  int64_t nnz = 0;
+  check_rc(tgnx_pair_index_build(src.data_ptr<int64_t>(), dst.data_ptr<int64_t>(), n, num_nodes,
+                                 indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), first.data_ptr<int64_t>(), &nnz,
+                                 ws.data_ptr(), nb, cur_stream()),
+           "tgnx_pair_index_build");
+  return {indptr, indices.narrow(0, 0, nnz), first.narrow(0, 0, nnz)};
+}
+
+at::Tensor pair_index_contains(const at::Tensor& indptr, const at::Tensor& indices, const at::Tensor& first,
+                               const at::Tensor& src, const at::Tensor& dst, const c10::optional<at::Tensor>& before,
+                               int64_t before_all) {
+  dev_tensor(indptr, at::kLong, "indptr");
+  dev_tensor(indices, at::kLong, "indices");
+  dev_tensor(first, at::kLong, "first");
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(dst, at::kLong, "dst");
+  same_device(indptr, {&indices, &first, &src, &dst});
+  const int64_t n = src.numel();
+  TORCH_CHECK(dst.numel() == n && first.numel() == indices.numel() && indptr.numel() >= 2, "pair_index_contains: shapes");
+  const int64_t* pb = nullptr;
+  if (before.has_value()) {
+    dev_tensor(*before, at::kLong, "before");
+    same_device(indptr, {&*before});
+    TORCH_CHECK(before->numel() == n, "one row cut per query");
+    pb = before->data_ptr<int64_t>();
+  }
+  const c10::OptionalDeviceGuard guard(indptr.device());
+  at::Tensor out = at::empty({n}, src.options().dtype(at::kBool));
+  check_rc(tgnx_pair_index_contains(indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), first.data_ptr<int64_t>(),
+                                    indptr.numel() - 1, src.data_ptr<int64_t>(), dst.data_ptr<int64_t>(), n, pb,
+                                    before_all, reinterpret_cast<uint8_t*>(out.data_ptr<bool>()), cur_stream()),
+           "tgnx_pair_index_contains");
+  return out;
+}
+
+// (rows [hi - lo, k], k_hist int32[hi - lo], status int64[4] on the device: the caller reads it)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> negs_hist_rnd(const at::Tensor& src, const at::Tensor& dst,
+                                                             const at::Tensor& t, int64_t lo, int64_t hi, int64_t k,
+                                                             int64_t q, int64_t hist_hi, const at::Tensor& indptr,
+                                                             const at::Tensor& indices, const at::Tensor& first,
+                                                             const at::Tensor& pool, int64_t seed, int64_t max_draws) {
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(dst, at::kLong, "dst");
+  TORCH_CHECK(t.scalar_type() == at::kDouble || t.scalar_type() == at::kFloat, "t must be float64 or float32");
+  dev_tensor(t, t.scalar_type(), "t");
+  dev_tensor(indptr, at::kLong, "indptr");
+  dev_tensor(indices, at::kLong, "indices");
+  dev_tensor(first, at::kLong, "first");
+  dev_tensor(pool, at::kLong, "pool");
+  same_device(src, {&dst, &t, &indptr, &indices, &first, &pool});
+  const int64_t E = src.numel();
+  TORCH_CHECK(dst.numel() == E && t.numel() == E && first.numel() == indices.numel() && indptr.numel() >= 2,
+              "negs_hist_rnd: shapes");
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= E, "rows [lo, hi) outside the event table");
+  TORCH_CHECK(k >= 1 && k <= 1024 && q >= 0 && q <= k, "negs_hist_rnd: k must be in [1, 1024] and q in [0, k]");
+  const c10::OptionalDeviceGuard guard(src.device());
+  auto lopt = src.options();
+  at::Tensor out = at::empty({hi - lo, k}, lopt), k_hist = at::empty({hi - lo}, lopt.dtype(at::kInt));
+  at::Tensor status = at::empty({4}, lopt);
+  const size_t nb = tgnx_negs_hist_rnd_ws_bytes(indices.numel(), hi - lo);
+  at::Tensor ws = at::empty({(int64_t)std::max<size_t>(nb, 1)}, lopt.dtype(at::kByte));
+  check_rc(tgnx_negs_hist_rnd(src.data_ptr<int64_t>(), dst.data_ptr<int64_t>(), t.data_ptr(),
+                              t.scalar_type() == at::kDouble ? 1 : 0, E, lo, hi, (int32_t)k, (int32_t)q, hist_hi,
+                              indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), first.data_ptr<int64_t>(),
+                              indptr.numel() - 1, indices.numel(), pool.data_ptr<int64_t>(), pool.numel(), (uint64_t)seed,
+                              max_draws, out.data_ptr<int64_t>(), k_hist.data_ptr<int32_t>(), status.data_ptr<int64_t>(),
+                              ws.data_ptr(), nb, cur_stream()),
+           "tgnx_negs_hist_rnd");
+  return {out, k_hist, status};
 }
 
 at::Tensor gemm_f32(const at::Tensor& A, const at::Tensor& B, const c10::optional<at::Tensor>& bias, bool trans_a,
@@ -952,6 +1039,13 @@ TORCH_LIBRARY(tgnx, m) {
   m.def("tcsr_sample(Tensor indptr, Tensor indices, Tensor eid, Tensor ts, int K, Tensor roots, int mode, Tensor cut) "
         "-> (Tensor, Tensor, Tensor, Tensor)",
         &tcsr_sample);
+  m.def("pair_index_build(Tensor src, Tensor dst, int num_nodes) -> (Tensor, Tensor, Tensor)", &pair_index_build);
+  m.def("pair_index_contains(Tensor indptr, Tensor indices, Tensor first, Tensor src, Tensor dst, Tensor? before=None, "
+        "int before_all=9223372036854775807) -> Tensor",
+        &pair_index_contains);
+  m.def("negs_hist_rnd(Tensor src, Tensor dst, Tensor t, int lo, int hi, int k, int q, int hist_hi, Tensor indptr, "
+        "Tensor indices, Tensor first, Tensor pool, int seed=0, int max_draws=0) -> (Tensor, Tensor, Tensor)",
+        &negs_hist_rnd);
   m.def("gemm_f32(Tensor A, Tensor B, Tensor? bias=None, bool trans_a=False, bool trans_b=False) -> Tensor", &gemm_f32);
   // SURVEY §8b's names for the sampler ops (the same functions as ring_sample / ring_insert / ring_reset)
   m.def("sample_recent(Tensor nbr, Tensor e_id, Tensor t, Tensor(a!) assoc, Tensor n_id) -> "

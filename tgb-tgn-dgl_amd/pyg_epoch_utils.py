@@ -7,3 +7,4 @@ from tgnx.tgn_epoch import grow_nodes, observe_grow  # noqa: F401
 from tgnx.tgn_epoch import embedding_table  # noqa: F401
 from tgnx.tgn_epoch import similar  # noqa: F401
 from tgnx.tgn_epoch import forget  # noqa: F401
+from tgnx.tgn_epoch import edgebank, tgb_negatives  # noqa: F401

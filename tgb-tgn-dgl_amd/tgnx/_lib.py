@@ -83,6 +83,13 @@ SIGNATURES = {
     "tgnx_tcsr_build_ws_bytes": (c_sz, [c_i64, c_i32]),
     "tgnx_tcsr_build": (ctypes.c_int, [P, P, P, c_i64, c_i64, c_i32, P, P, P, P, P, P, c_sz, c_vp]),
     "tgnx_tcsr_sample": (ctypes.c_int, [P, P, P, P, c_i64, c_i32, P, c_i64, c_i32, P, c_i64, P, P, P, P, P, c_vp]),
+    # pair index and hist_rnd evaluation negatives (tgnx_negs.hip)
+    "tgnx_pair_index_build_ws_bytes": (c_sz, [c_i64]),
+    "tgnx_pair_index_build": (ctypes.c_int, [P, P, c_i64, c_i64, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_pair_index_contains": (ctypes.c_int, [P, P, P, c_i64, P, P, c_i64, P, c_i64, P, c_vp]),
+    "tgnx_negs_hist_rnd_ws_bytes": (c_sz, [c_i64, c_i64]),
+    "tgnx_negs_hist_rnd": (ctypes.c_int, [P, P, P, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, P, P, P, c_i64,
+                                          c_i64, P, c_i64, c_u64, c_i64, P, P, P, P, c_sz, c_vp]),
     "tgnx_gemm_f32_ws_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "tgnx_gemm_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i64, c_i32, P, c_i64, c_i32, P, c_i64, P, c_i32, P, c_sz,
                                      c_vp]),

@@ -192,13 +192,42 @@ class Evaluator:
         return {"mrr": float((1.0 / rank).mean())}
 
 
+def _neg_strategy() -> str:
+    """TGNX_EVAL_NEG_STRATEGY: unset / "uniform" (the default: uniform destinations) or "hist_rnd" (TGB's protocol,
+    generated on the device by tgnx.tgb_negs when no negatives table came with the data)."""
+    s = os.environ.get("TGNX_EVAL_NEG_STRATEGY", "") or "uniform"
+    if s not in ("uniform", "hist_rnd"):
+        raise ValueError(f"TGNX_EVAL_NEG_STRATEGY must be 'uniform' or 'hist_rnd', got {s!r}")
+    return s
+
+
+def _hist_rnd_negatives(src, dst, t, tr: int, va: int, kneg: int, have=()) -> dict:
+    """val_neg / test_neg (those not in `have`) as TGB's hist_rnd lists: per split, history = everything before it."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("TGNX_EVAL_NEG_STRATEGY=hist_rnd generates the evaluation negatives on the device "
+                           "(tgnx.tgb_negs) and no HIP device is visible; unset it for uniform negatives")
+    from .tgb_negs import PairHistory, tgb_negatives
+    dev = torch.device("cuda")
+    s, d = torch.from_numpy(np.asarray(src, np.int64)).to(dev), torch.from_numpy(np.asarray(dst, np.int64)).to(dev)
+    tt = torch.from_numpy(np.asarray(t, np.float64)).to(dev)
+    idx = PairHistory.build(s, d)
+    out = {}
+    for key, lo, hi, seed in (("val_neg", tr, va, 1), ("test_neg", va, len(src), 2)):
+        if key not in have:
+            out[key] = tgb_negatives(s, d, tt, lo, hi, kneg, seed=seed, index=idx).cpu().numpy()
+    return out
+
+
 def _load(name: str):
+    strategy = _neg_strategy()
     if os.path.exists(name) and name.endswith(".npz"):
         z = np.load(name, allow_pickle=False)
         src, dst, t, msg = z["src"], z["dst"], z["t"], z["msg"]
         E = src.shape[0]
         tr, va = int(round(0.70 * E)), int(round(0.85 * E))
         negs = {k: z[k] for k in ("val_neg", "test_neg") if k in z.files}
+        if strategy == "hist_rnd" and len(negs) < 2:
+            negs.update(_hist_rnd_negatives(src, dst, t, tr, va, int(os.environ.get("TGNX_EVAL_NEGS", "100")), negs))
         return src, dst, t, msg, tr, va, negs, None
     if name not in SHAPES:
         raise ValueError(f"unknown dataset {name!r}: give a TGB name {sorted(SHAPES)} or an .npz path")
@@ -208,6 +237,8 @@ def _load(name: str):
     if disk is not None:
         src, dst, t, msg, tr, va, negs = disk
         kneg = int(os.environ.get("TGNX_EVAL_NEGS", str(SHAPES[name].num_neg_eval)))
+        if strategy == "hist_rnd" and len(negs) < 2:
+            negs.update(_hist_rnd_negatives(src, dst, t, tr, va, kneg, negs))
         if "val_neg" not in negs:
             negs["val_neg"] = uniform_negatives(dst, tr, va, kneg, seed=1)
         if "test_neg" not in negs:
@@ -217,7 +248,10 @@ def _load(name: str):
     s = make_stream(SHAPES[name], seed=int(os.environ.get("TGNX_SYNTH_SEED", "0")),
                     num_events=int(ev) if ev else None)
     kneg = int(os.environ.get("TGNX_EVAL_NEGS", str(s.shape.num_neg_eval)))
-    negs = {"val_neg": eval_negatives(s, "val", kneg), "test_neg": eval_negatives(s, "test", kneg)}
+    if strategy == "hist_rnd":
+        negs = _hist_rnd_negatives(s.src, s.dst, s.t, s.train_end, s.val_end, kneg)
+    else:
+        negs = {"val_neg": eval_negatives(s, "val", kneg), "test_neg": eval_negatives(s, "test", kneg)}
     return s.src, s.dst, s.t, s.msg, s.train_end, s.val_end, negs, s
 
 

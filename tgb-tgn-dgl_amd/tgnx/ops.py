@@ -35,7 +35,8 @@ OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "t
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
-       "memstore_put", "memstore_count", "memstore_gather", "memstore_build_msg")
+       "memstore_put", "memstore_count", "memstore_gather", "memstore_build_msg",
+       "pair_index_build", "pair_index_contains", "negs_hist_rnd")
 _loaded = False
 
 

@@ -121,7 +121,8 @@ def eval_negatives(stream: TemporalStream, split: str, num_neg: int | None = Non
     """Per-positive eval negatives drawn from the destination set, excluding the positive.
 
     Stands in for TGB's precomputed `*_ns.pkl` (`epoch_utils.py:43`): Long[E_split, num_neg]
-    (the split's first `limit` events only, if given).
+    (the split's first `limit` events only, if given).  Uniform draws; TGB's hist_rnd lists come from
+    tgnx.tgb_negs (TGNX_EVAL_NEG_STRATEGY=hist_rnd in tgnx.data).
     """
     sl = stream.split(split)
     pos = stream.dst[sl]

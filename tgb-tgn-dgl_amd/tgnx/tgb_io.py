@@ -104,7 +104,8 @@ def _negatives_from_pickle(path: str, src, dst, t, lo: int, hi: int) -> np.ndarr
 def uniform_negatives(dst: np.ndarray, lo: int, hi: int, k: int, seed: int = 0) -> np.ndarray:
     """Stand-in evaluation negatives when the TGB *_ns.pkl files are absent: k destinations per event of
     [lo, hi), uniform over the stream's destination set, redrawn where equal to the positive (TGB's own
-    lists mix historical and random destinations; they cannot be regenerated here)."""
+    lists mix historical and random destinations: tgnx.tgb_negs generates those on the device, opt-in through
+    TGNX_EVAL_NEG_STRATEGY=hist_rnd)."""
     rng = np.random.default_rng(seed)
     pool = np.unique(dst)
     out = pool[rng.integers(0, pool.size, size=(hi - lo, k))]

@@ -1089,7 +1089,7 @@ class TgnEngine:
         self._group = None
         self._release_plan_table()
         for a in ("_res_buf", "_buf_ref", "_res", "_res_drop", "_res_fused", "_f", "_cfg_ref", "_ctl_p", "_pending",
-                  "_ev_buf", "_ev_buf_ref", "_ev_negs", "_ev_rr", "_keep"):
+                  "_ev_buf", "_ev_buf_ref", "_ev_negs", "_ev_rr", "_keep", "_pair_hist"):
             self.__dict__.pop(a, None)
         self._ev = None
         self._ev_graphs = None
@@ -1755,6 +1755,31 @@ class TgnEngine:
                             q_key=nodes if exclude_self else None, exclude=None if ex is None else ex[:2],
                             validate=False)
         return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
+
+    # ------------------------------------------------------------------ hist_rnd evaluation negatives
+    def pair_history(self):
+        """The tgnx.tgb_negs.PairHistory over the resident event table: each source's distinct destinations and the
+        first row of every pair.  Built on first use, rebuilt when num_events changed (append_events), dropped with the
+        bindings by compact_events, forget_nodes and load_stream_state (they renumber or rewrite the rows)."""
+        from .tgb_negs import PairHistory
+        idx = self.__dict__.get("_pair_hist")
+        if idx is None or idx.num_rows != self.num_events or idx.num_nodes != int(self.cfg.num_nodes):
+            idx = PairHistory.build(self.src, self.dst, int(self.cfg.num_nodes))
+            self._pair_hist = idx
+        return idx
+
+    def eval_negatives(self, lo: int, hi: int, k: int, *, hist_ratio: float = 0.5, hist_hi=None, seed: int = 0,
+                       max_draws: int = 0) -> torch.Tensor:
+        """TGB-style hist_rnd negatives for rows [lo, hi) of the resident table (tgnx.tgb_negs.tgb_negatives on the
+        resident src / dst / t, the engine's dst_nodes as the pool, pair_history() as the index): int64 [hi - lo, k] on
+        the device, the table bind_eval_resident takes.  The resident t is float32: a stream whose timestamps float32
+        merges should generate from its float64 times (pyg_epoch_utils.tgb_negatives does).  World 1 only."""
+        from .tgb_negs import tgb_negatives
+        if self.world != 1:
+            raise ValueError("eval_negatives: one device only (world 1)")
+        pool = None if self.dst_nodes is None else torch.unique(self.dst_nodes)
+        return tgb_negatives(self.src, self.dst, self.t, lo, hi, k, hist_ratio=hist_ratio, hist_hi=hist_hi, pool=pool,
+                             seed=seed, index=self.pair_history(), max_draws=max_draws)
 
     # ------------------------------------------------------------------ resident eval pass
     def bind_eval_resident(self, split_lo: int, split_hi: int, batch: int, negs):

@@ -33,6 +33,9 @@ updates the stores, the memory and the ring in eval order.
       and renumber the rest in order (TgnEngine.compact_events); kept[new] = old
   forget(model, neighbor_loader, ids, compact=False, drop_candidates=False) -> counts: erase nodes from memory, ring
       and stores in place (TgnEngine.forget_nodes)
+  tgb_negatives(loader, k, hist_ratio=0.5, ...) -> [hi - lo, k]: TGB's hist_rnd evaluation negatives for a split,
+      generated on the device and installed as loader.negatives (tgnx.tgb_negs); edgebank(loader, batch=None) -> the
+      MRR of the memorisation baseline EdgeBank-inf under the loader's negatives
   save_stream(model, neighbor_loader, f) / load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
       the whole stream state (table, memory, stores, ring, ctl; TgnEngine.stream_state) to / from a torch.save file
 
@@ -378,6 +381,49 @@ def forget(model, neighbor_loader, ids, compact=False, drop_candidates=False):
     out = eng.forget_nodes(ids, compact=compact, drop_candidates=drop_candidates)
     neighbor_loader.cur_e_id = eng.num_events
     return out
+
+
+def _pair_history(data, device):
+    """The PairHistory over a TemporalData's whole stream on `device`, built once and kept on the data object."""
+    from .tgb_negs import PairHistory
+    dev = torch.device(device)
+    idx = getattr(data, "_tgnx_pair_hist", None)
+    if idx is None or idx.num_rows != data.num_events or idx.device.type != dev.type:
+        idx = PairHistory.build(data.src, data.dst, data.num_nodes, device=dev)
+        data._tgnx_pair_hist = idx
+    return idx
+
+
+@torch.no_grad()
+def tgb_negatives(loader, k, *, hist_ratio=0.5, hist_hi=None, pool=None, seed=0, device="cuda"):
+    """TGB's hist_rnd evaluation negatives for a SplitLoader's split, generated on the device from the stream's float64
+    timestamps (tgnx.tgb_negs.tgb_negatives: per event int(k * hist_ratio) destinations its source met before the split
+    and is not meeting now, the rest random destinations that are neither) and installed as loader.negatives, so that
+    test() takes the resident pass on them.  Returns the [hi - lo, k] table (on the device)."""
+    from .tgb_negs import tgb_negatives as generate
+    if not isinstance(loader, SplitLoader):
+        raise TypeError("tgnx tgb_negatives needs a tgnx.data.SplitLoader")
+    d = loader.data
+    negs = generate(d.src, d.dst, d.t.double(), loader.lo, loader.hi, k, hist_ratio=hist_ratio, hist_hi=hist_hi,
+                    pool=pool, seed=seed, index=_pair_history(d, device))
+    loader.negatives = negs
+    loader._dev = {}                                      # (resident() caches the negatives it moved)
+    return negs
+
+
+@torch.no_grad()
+def edgebank(loader, batch=None, device="cuda"):
+    """The MRR of EdgeBank-inf (TGB's memorisation baseline: a pair scores 1 if it occurred before the start row of its
+    batch, else 0) over a SplitLoader's split under loader.negatives, in batches of `batch` (default: the loader's):
+    the number to hold a model's test() MRR on the same negatives against.  Two PairHistory.contains calls plus
+    torch (tgnx.tgb_negs.edgebank_mrr)."""
+    from .tgb_negs import edgebank_mrr
+    negs = loader.negatives
+    if not (torch.is_tensor(negs) and negs.dim() == 2 and negs.shape[0] == loader.hi - loader.lo):
+        raise ValueError("tgnx edgebank needs a rectangular negatives table on the loader ([hi - lo, K])")
+    d = loader.data
+    return edgebank_mrr(_pair_history(d, device), d.src, d.dst, negs, loader.lo, loader.hi,
+                        loader.batch_size if batch is None else int(batch))
 
 
 @torch.no_grad()
