@@ -1082,6 +1082,45 @@ int tgnx_memstore_build_msg(const int64_t* slot, int64_t n_msg, int64_t n_s, con
                             int64_t emb_rows, const int64_t* assoc, const int64_t* stamp, const int64_t* n_id, int64_t M,
                             int32_t emb_flags, float* out, float* t_rel, void* stream);
 
+/* ---------------------------------------------------------------- node property prediction (csrc/tgnx_nodeprop.hip)
+ * NodePredictor (modules/decoder.py:30-41), its soft-target cross-entropy and NDCG@k (TGB's tgbn-* task).  Row-major
+ * fp32, caller-provided workspace, no allocation, no float atomics: every result is run-to-run bit-identical and
+ * independent of the grid. */
+#define TGNX_NODE_MAX_D 128
+#define TGNX_NODE_MAX_C 4096
+#define TGNX_NODE_MAX_K 128
+
+/* logits [M,C] = W2 relu(W1 z + b1) + b2 for z [M,D], w1 [D,D], w2 [C,D] (torch Linear layout), b1 [D] / b2 [C]
+ * (either may be NULL).  Two launches of the f32 MFMA GEMM core, bias and ReLU in their epilogues.  h [M,D] (the
+ * hidden rows relu(W1 z + b1), what the backward needs) is written when non-NULL; otherwise the hidden rows stay in
+ * the workspace.  1 <= D <= TGNX_NODE_MAX_D, 1 <= C <= TGNX_NODE_MAX_C, 0 <= M < 2^24. */
+size_t tgnx_node_predictor_ws_bytes(int64_t M, int64_t D, int64_t C);
+int tgnx_node_predictor(int64_t M, int64_t D, int64_t C, const float* z, const float* w1, const float* b1,
+                        const float* w2, const float* b2, float* logits, float* h, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/* Backward given dlogits [M,C] and the saved z, h: dw2 [C,D] = dlogits^T h, db2 [C], dh = (dlogits W2) (h > 0) (the
+ * mask in the GEMM's epilogue), dw1 [D,D] = dh^T z, db1 [D], dz [M,D] = dh W1.  Any output pointer may be NULL.
+ * M = 0 zeroes the parameter gradients.  ws: tgnx_node_predictor_bwd_ws_bytes bytes. */
+size_t tgnx_node_predictor_bwd_ws_bytes(int64_t M, int64_t D, int64_t C);
+int tgnx_node_predictor_bwd(int64_t M, int64_t D, int64_t C, const float* dlogits, const float* z, const float* h,
+                            const float* w1, const float* w2, float* dz, float* dw1, float* db1, float* dw2,
+                            float* db2, void* ws, size_t ws_bytes, void* stream);
+
+/* One pass over each row of logits [M,C] against dense targets y [M,C] (>= 0, any row sum), a wave per row:
+ *   loss_rows[i] = lse_i Σ_c y_ic − Σ_c y_ic l_ic                      (soft-target cross-entropy of the row)
+ *   dlogits[i,c] = (softmax(l_i)_c Σ_c' y_ic' − y_ic) scale            (scale = 1 / M for the mean loss)
+ *   ndcg[i]      = sklearn's ndcg_score(y_i, l_i, k) with tie averaging, float64: with gt_c / eq_c the classes
+ *                  scoring above / equal to c (c included), DCG = Σ_{c: y_c > 0} y_c (cum[min(gt_c + eq_c, k)] −
+ *                  cum[min(gt_c, k)]) / eq_c, IDCG the same with y ranked by itself, 0 where IDCG = 0.
+ * cum: k + 1 doubles on the device, cum[j] = Σ_{r=1..j} 1 / log2(r + 1) computed by the host.  Each of loss_rows,
+ * loss_mean (one float: scale Σ_i loss_rows[i] in a fixed order, a second one-workgroup launch; needs loss_rows),
+ * dlogits and ndcg may be NULL.  Row sums run lane-strided over the 64-class chunks in order, then across the wave;
+ * DCG / IDCG add their float64 terms in class order.  1 <= C <= TGNX_NODE_MAX_C, 1 <= k <= TGNX_NODE_MAX_K.  Rows
+ * whose logits are all -inf or hold a NaN are outside the domain. */
+int tgnx_node_loss_ndcg(int64_t M, int64_t C, int32_t k, const float* logits, const float* y, const double* cum,
+                        float scale, float* loss_rows, float* loss_mean, float* dlogits, double* ndcg, void* stream);
+
 /* ---------------------------------------------------------------- test hooks
  * The GEMM core (csrc/tgnx_gemm.h) on each tile config the library compiles, for tests/test_gpu_gemm_core.py; no
  * product path calls these.  cfg picks the config through the alias the step itself uses (so a build-variant

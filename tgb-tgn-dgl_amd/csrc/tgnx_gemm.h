@@ -148,6 +148,15 @@ inline GemmShape gemm_shape_split(int M, int N, int K, const int* Mdev, const in
   g.deferred = 1;
   return g;
 }
+// Shape policy of the stand-alone GEMMs (tgnx_gemm_f32, the node predictor's epilogue GEMMs): 64x64 tiles (G64)
+// once those already fill the chip, else the 16x16 wave-split tiles with direct operands (GD); K up to 4 chunks: one
+// workgroup per tile loops over K; larger K: split-K partials + a fixup launch.
+inline bool gemm_api_big(int64_t M, int64_t N) { return ((M + 63) / 64) * ((N + 63) / 64) >= 512; }
+template <class CFG>
+inline GemmShape gemm_api_shape(int64_t M, int64_t N, int64_t K) {
+  if (K <= 4 * CFG::KC) return gemm_shape<CFG>((int)M, (int)N, (int)K);
+  return gemm_shape_split<CFG>((int)M, (int)N, (int)K, nullptr, nullptr, nullptr, 16);
+}
 // grid of a GEMM: tiles x splits of the CAPACITY shape, padded to a multiple of the 8 XCDs (see gemm_work),
 // capped: capacities are worst cases (a 2-hop sample is sized for 2e5 rows and runs ~1e3), and
 // dispatching 1e5 workgroups that exit at once cost ~80 us per launch; a workgroup loops over the

@@ -3,21 +3,14 @@
 
 using namespace tgnx;
 
-// Tile config: 64x64 once that already fills the chip, else 16x16 wave-split tiles with direct operands (the
-// TGN step's long-K config, GemmCfg::DR: this entry point is also its unit test against torch).  K up to 4
-// chunks: one workgroup per tile loops over K; larger K: split-K partials + a fixup launch.
-static bool api_big(int64_t M, int64_t N) { return ((M + 63) / 64) * ((N + 63) / 64) >= 512; }
-template <class CFG>
-static GemmShape gemm_api_shape(int64_t M, int64_t N, int64_t K) {
-  if (K <= 4 * CFG::KC) return gemm_shape<CFG>((int)M, (int)N, (int)K);
-  return gemm_shape_split<CFG>((int)M, (int)N, (int)K, nullptr, nullptr, nullptr, 16);
-}
+// Tile config and K split: gemm_api_big / gemm_api_shape (tgnx_gemm.h).  The 16x16 wave-split config with direct
+// operands is the TGN step's long-K config (GemmCfg::DR): this entry point is also its unit test against torch.
 
 extern "C" {
 
 size_t tgnx_gemm_f32_ws_bytes(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return 256;
-  const GemmShape g = api_big(M, N) ? gemm_api_shape<G64>(M, N, K) : gemm_api_shape<GD>(M, N, K);
+  const GemmShape g = gemm_api_big(M, N) ? gemm_api_shape<G64>(M, N, K) : gemm_api_shape<GD>(M, N, K);
   return gemm_partial_floats(g) * 4 + 256;
 }
 
@@ -42,7 +35,7 @@ int tgnx_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, 
     if (g.deferred) gemm_fixup_launch(0, NoTail{}, s, gemm_fix<CFG>(g, part, epi));
   };
   auto run = [&](const auto& al, const auto& bl) {
-    if (api_big(M, N)) run2(G64{}, al, bl);
+    if (gemm_api_big(M, N)) run2(G64{}, al, bl);
     else run2(GD{}, al, bl);
   };
   if (!trans_a && trans_b)

@@ -768,6 +768,85 @@ predictor_bwd(const at::Tensor& dout, const at::Tensor& z_src, const at::Tensor&
   return {dzs, dzd, dws, dbs, dwd, dbd, dwo, dbo};
 }
 
+// NodePredictor (decoder.py:30-41; csrc/tgnx_nodeprop.hip): (logits [M, C], h [M, D] or an empty tensor)
+void node_head_args(const at::Tensor& z, const at::Tensor& w1, const at::Tensor& w2) {
+  dev_tensor(z, at::kFloat, "z");
+  dev_tensor(w1, at::kFloat, "w1");
+  dev_tensor(w2, at::kFloat, "w2");
+  TORCH_CHECK(z.dim() == 2 && w1.dim() == 2 && w2.dim() == 2, "z [M, D], w1 [D, D], w2 [C, D]");
+  const int64_t D = z.size(1);
+  TORCH_CHECK(w1.size(0) == D && w1.size(1) == D && w2.size(1) == D, "z [M, D], w1 [D, D], w2 [C, D]");
+  same_device(z, {&w1, &w2});
+}
+
+std::tuple<at::Tensor, at::Tensor> node_predictor(const at::Tensor& z, const at::Tensor& w1,
+                                                  const c10::optional<at::Tensor>& b1, const at::Tensor& w2,
+                                                  const c10::optional<at::Tensor>& b2, bool need_h) {
+  node_head_args(z, w1, w2);
+  const int64_t M = z.size(0), D = z.size(1), C = w2.size(0);
+  const float* p1 = opt_ptr(b1, z, D, "b1");
+  const float* p2 = opt_ptr(b2, z, C, "b2");
+  const c10::OptionalDeviceGuard guard(z.device());
+  at::Tensor logits = at::empty({M, C}, z.options()), h = grad_like(need_h, {M, D}, z);
+  const size_t nb = tgnx_node_predictor_ws_bytes(M, D, C);
+  at::Tensor ws = ws_bytes(z, nb);
+  check_rc(tgnx_node_predictor(M, D, C, z.data_ptr<float>(), w1.data_ptr<float>(), p1, w2.data_ptr<float>(), p2,
+                               logits.data_ptr<float>(), grad_ptr(need_h, h), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_node_predictor");
+  return {logits, h};
+}
+
+// (dz, dw1, db1, dw2, db2); an empty tensor for a gradient that need[i] = 0 leaves out
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> node_predictor_bwd(
+    const at::Tensor& dlogits, const at::Tensor& z, const at::Tensor& h, const at::Tensor& w1, const at::Tensor& w2,
+    at::IntArrayRef need) {
+  node_head_args(z, w1, w2);
+  dev_tensor(dlogits, at::kFloat, "dlogits");
+  dev_tensor(h, at::kFloat, "h");
+  TORCH_CHECK(need.size() == 5, "need must have 5 entries (dz, dw1, db1, dw2, db2)");
+  const int64_t M = z.size(0), D = z.size(1), C = w2.size(0);
+  TORCH_CHECK(dlogits.dim() == 2 && dlogits.size(0) == M && dlogits.size(1) == C, "dlogits must be [M, C]");
+  TORCH_CHECK(h.dim() == 2 && h.size(0) == M && h.size(1) == D, "h must be [M, D] (the forward's hidden rows)");
+  same_device(z, {&dlogits, &h});
+  const c10::OptionalDeviceGuard guard(z.device());
+  at::Tensor dz = grad_like(need[0], z.sizes(), z), dw1 = grad_like(need[1], w1.sizes(), z);
+  at::Tensor db1 = grad_like(need[2], {D}, z), dw2 = grad_like(need[3], w2.sizes(), z), db2 = grad_like(need[4], {C}, z);
+  const size_t nb = tgnx_node_predictor_bwd_ws_bytes(M, D, C);
+  at::Tensor ws = ws_bytes(z, nb);
+  check_rc(tgnx_node_predictor_bwd(M, D, C, dlogits.data_ptr<float>(), z.data_ptr<float>(), h.data_ptr<float>(),
+                                   w1.data_ptr<float>(), w2.data_ptr<float>(), grad_ptr(need[0], dz),
+                                   grad_ptr(need[1], dw1), grad_ptr(need[2], db1), grad_ptr(need[3], dw2),
+                                   grad_ptr(need[4], db2), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_node_predictor_bwd");
+  return {dz, dw1, db1, dw2, db2};
+}
+
+// the row kernel (tgnx_node_loss_ndcg): (mean loss [], loss rows [M], dlogits [M, C], ndcg float64 [M]); a part that
+// is not asked for comes back as an empty tensor.  cum: k + 1 float64 on the device (tgnx/ops.py builds it).
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> node_loss_ndcg(const at::Tensor& logits, const at::Tensor& y,
+                                                                          const at::Tensor& cum, int64_t k,
+                                                                          bool need_loss, bool need_grad,
+                                                                          bool need_ndcg) {
+  dev_tensor(logits, at::kFloat, "logits");
+  dev_tensor(y, at::kFloat, "y");
+  dev_tensor(cum, at::kDouble, "cum");
+  TORCH_CHECK(logits.dim() == 2 && y.sizes() == logits.sizes(), "logits and y must be [M, C]");
+  TORCH_CHECK(k >= 1 && k <= TGNX_NODE_MAX_K, "k must be in [1, ", TGNX_NODE_MAX_K, "], got ", k);
+  TORCH_CHECK(cum.numel() == k + 1, "cum must have k + 1 entries");
+  same_device(logits, {&y, &cum});
+  const int64_t M = logits.size(0), C = logits.size(1);
+  const c10::OptionalDeviceGuard guard(logits.device());
+  at::Tensor mean = grad_like(need_loss, {}, logits), rows = grad_like(need_loss, {M}, logits);
+  at::Tensor dl = grad_like(need_grad, logits.sizes(), logits);
+  at::Tensor nd = need_ndcg ? at::empty({M}, cum.options()) : at::empty({0}, cum.options());
+  check_rc(tgnx_node_loss_ndcg(M, C, (int32_t)k, logits.data_ptr<float>(), y.data_ptr<float>(),
+                               cum.data_ptr<double>(), M > 0 ? 1.0f / (float)M : 0.0f, grad_ptr(need_loss, rows),
+                               grad_ptr(need_loss, mean), grad_ptr(need_grad, dl),
+                               need_ndcg ? nd.data_ptr<double>() : nullptr, cur_stream()),
+           "tgnx_node_loss_ndcg");
+  return {mean, rows, dl, nd};
+}
+
 // t [n]; w ([D] or Linear(1, D)'s [D, 1]) and b [D]
 int64_t time_args(const at::Tensor& t, const at::Tensor& w, const at::Tensor& b) {
   dev_tensor(t, at::kFloat, "t");
@@ -1095,6 +1174,15 @@ TORCH_LIBRARY(tgnx, m) {
         "Tensor? b_dst, Tensor w_out, Tensor b_out, bool sigmoid, int[] need) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
         &predictor_bwd);
+  // node property prediction (csrc/tgnx_nodeprop.hip)
+  m.def("node_predictor(Tensor z, Tensor w1, Tensor? b1, Tensor w2, Tensor? b2, bool need_h) -> (Tensor, Tensor)",
+        &node_predictor);
+  m.def("node_predictor_bwd(Tensor dlogits, Tensor z, Tensor h, Tensor w1, Tensor w2, int[] need) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor)",
+        &node_predictor_bwd);
+  m.def("node_loss_ndcg(Tensor logits, Tensor y, Tensor cum, int k, bool need_loss, bool need_grad, bool need_ndcg) "
+        "-> (Tensor, Tensor, Tensor, Tensor)",
+        &node_loss_ndcg);
   m.def("time_encode(Tensor t, Tensor w, Tensor b) -> Tensor", &time_encode);
   m.def("time_encode_bwd(Tensor dout, Tensor t, Tensor w, Tensor b) -> (Tensor, Tensor)", &time_encode_bwd);
   m.def("time_embedding(Tensor x, Tensor rel_t, Tensor w, Tensor b) -> Tensor", &time_embedding);

@@ -1,2 +1,2 @@
 """Drop-in for the reference's modules/decoder.py — tgnx HIP path (forward and backward)."""
-from tgnx.nn import LinkPredictor  # noqa: F401
+from tgnx.nn import LinkPredictor, NodePredictor  # noqa: F401

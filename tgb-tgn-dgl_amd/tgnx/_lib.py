@@ -136,6 +136,12 @@ SIGNATURES = {
     "tgnx_msg_agg_last_bwd": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, P, c_vp]),
     "tgnx_msg_agg_mean_bwd_ws_bytes": (c_sz, [c_i64]),
     "tgnx_msg_agg_mean_bwd": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, P, P, P, c_sz, c_vp]),
+    # node property prediction (tgnx_nodeprop.hip)
+    "tgnx_node_predictor_ws_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "tgnx_node_predictor": (ctypes.c_int, [c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_node_predictor_bwd_ws_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "tgnx_node_predictor_bwd": (ctypes.c_int, [c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_node_loss_ndcg": (ctypes.c_int, [c_i64, c_i64, c_i32, P, P, P, ctypes.c_float, P, P, P, P, c_vp]),
     # device message store (tgnx_memstore.hip)
     "tgnx_memstore_put": (ctypes.c_int, [P, P, P, P, c_i64, c_i64, P, P, c_i64, c_i64, c_i64, P, P, P, P, P, P, P,
                                          c_vp]),

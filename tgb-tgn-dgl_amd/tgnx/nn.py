@@ -12,6 +12,7 @@ autograd functions of tgnx/ops.py (HIP kernels forward and backward; no eager-Py
     GraphAttentionEmbedding(in, out, msg_dim, time_enc)  modules/emb_module.py:11-29
     TimeEmbedding(in, out)                             modules/emb_module.py:32-52 (JODIE's projection)
     LinkPredictor(in_channels)                         modules/decoder.py:12-27
+    NodePredictor(in_dim, out_dim)                     modules/decoder.py:30-41 (TGB node property prediction)
     TGNMemory(num_nodes, raw_msg_dim, memory_dim, time_dim, message_module, aggregator_module,
               memory_updater_cell='gru')               modules/memory_module.py:25-215
     DyRepMemory(..., memory_updater_type, use_src_emb_in_msg=False, use_dst_emb_in_msg=False)
@@ -221,6 +222,19 @@ class LinkPredictor(nn.Module):
                              self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, target, **kw)
 
 
+class NodePredictor(nn.Module):
+    """modules/decoder.py:30-41: out(relu(lin_node(node_embed))), logits [M, out_dim] (no softmax, as the reference);
+    in_dim <= 128, out_dim <= 4096.  ops.soft_cross_entropy / ops.node_loss_ndcg are its loss and metric."""
+
+    def __init__(self, in_dim: int, out_dim: int):
+        super().__init__()
+        self.lin_node = nn.Linear(in_dim, in_dim)
+        self.out = nn.Linear(in_dim, out_dim)
+
+    def forward(self, node_embed):
+        return ops.node_predictor(node_embed, self.lin_node.weight, self.lin_node.bias, self.out.weight, self.out.bias)
+
+
 class TGNMemory(nn.Module):
     """modules/memory_module.py:25-215 over a device message store (csrc/tgnx_memstore.hip).
 
@@ -426,4 +440,4 @@ class DyRepMemory(TGNMemory):
 
 
 __all__ = ["TimeEncoder", "IdentityMessage", "LastAggregator", "MeanAggregator", "MemoryCell", "TransformerConv",
-           "GraphAttentionEmbedding", "TimeEmbedding", "LinkPredictor", "TGNMemory", "DyRepMemory"]
+           "GraphAttentionEmbedding", "TimeEmbedding", "LinkPredictor", "NodePredictor", "TGNMemory", "DyRepMemory"]

@@ -19,8 +19,10 @@ behind the autograd functions below — memory_cell, link_predictor, time_encode
 aggregate_mean, linear — which tgnx/nn.py's modules call.  memstore_put / memstore_count / memstore_gather /
 memstore_build_msg (csrc/tgnx_memstore.hip) are the device message store of tgnx.nn.TGNMemory / DyRepMemory
 (memory_module.py:140-145, :180-207); `build_messages` below is memstore_build_msg with the time encoder's
-gradient.  No CPU fallback: loading needs the built library
-(make -C tgb-tgn-dgl_amd) and the device ops need a HIP device.
+gradient.  node_predictor / node_predictor_bwd / node_loss_ndcg (csrc/tgnx_nodeprop.hip) are TGB's node property
+prediction: NodePredictor (decoder.py:30-41) and the row kernel giving soft-target cross-entropy, its gradient and
+NDCG@k in one pass; `node_predictor`, `soft_cross_entropy`, `ndcg_at_k`, `node_loss_ndcg` below.  No CPU fallback:
+loading needs the built library (make -C tgb-tgn-dgl_amd) and the device ops need a HIP device.
 """
 from __future__ import annotations
 
@@ -36,7 +38,8 @@ OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "t
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
        "memstore_put", "memstore_count", "memstore_gather", "memstore_build_msg",
-       "pair_index_build", "pair_index_contains", "negs_hist_rnd")
+       "pair_index_build", "pair_index_contains", "negs_hist_rnd",
+       "node_predictor", "node_predictor_bwd", "node_loss_ndcg")
 _loaded = False
 
 
@@ -415,3 +418,100 @@ def build_messages(w, b, slot, n_s, log_src, log_dst, log_t, log_raw, fill, memo
     to w and b through time_encode_bwd with the saved t_rel."""
     return _BuildMessages.apply(w.contiguous(), b.contiguous(), slot, int(n_s), log_src, log_dst, log_t, log_raw,
                                 int(fill), memory, last_update, emb, assoc, stamp, n_id, int(emb_flags))
+
+
+# ---------------------------------------------------------------------- node property prediction (tgnx_nodeprop.hip)
+NODE_MAX_K = 128                          # TGNX_NODE_MAX_K
+_ndcg_cum = {}
+
+
+def ndcg_cum(k: int):
+    """cum[j] = sum of the first j NDCG discounts 1 / log2(r + 1), j = 0..k, in float64 on the host (the device never
+    evaluates log2): a plain list."""
+    import math
+    cum = [0.0]
+    for r in range(1, int(k) + 1):
+        cum.append(cum[-1] + 1.0 / math.log2(r + 1))
+    return cum
+
+
+def _cum_on(k: int, device):
+    k = int(k)
+    if not 1 <= k <= NODE_MAX_K:
+        raise ValueError(f"ndcg: k must be in [1, {NODE_MAX_K}], got {k}")
+    key = (k, str(device))
+    if key not in _ndcg_cum:
+        _ndcg_cum[key] = torch.tensor(ndcg_cum(k), dtype=torch.float64, device=device)
+    return _ndcg_cum[key]
+
+
+class _NodePredictor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, w1, b1, w2, b2):
+        need_h = any(ctx.needs_input_grad)
+        logits, h = load().node_predictor(z, w1, b1, w2, b2, need_h)
+        if need_h:
+            ctx.save_for_backward(z, h, w1, w2)
+        ctx.has_b = (b1 is not None, b2 is not None)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        z, h, w1, w2 = ctx.saved_tensors
+        nz, nw1, nb1, nw2, nb2 = (int(v) for v in ctx.needs_input_grad)
+        need = [nz, nw1, nb1 and int(ctx.has_b[0]), nw2, nb2 and int(ctx.has_b[1])]
+        dz, dw1, db1, dw2, db2 = _grads(load().node_predictor_bwd(dlogits.contiguous(), z, h, w1, w2, need), need)
+        return dz, dw1, db1, dw2, db2
+
+
+def node_predictor(z, w1, b1, w2, b2):
+    """NodePredictor (decoder.py:30-41): logits [M, C] = W2 relu(W1 z + b1) + b2 for z [M, D], w1 [D, D], w2 [C, D]
+    (D <= 128, C <= 4096), two launches of the f32 MFMA GEMM with bias and ReLU in the epilogues; the hidden rows are
+    kept only when a gradient is needed.  Gradients flow to every tensor (dz too, so a composed model trains through
+    the head)."""
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    return _NodePredictor.apply(c(z), c(w1), c(b1), c(w2), c(b2))
+
+
+class _NodeLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, y, k):
+        need_grad = ctx.needs_input_grad[0]
+        want_ndcg = k is not None
+        cum = _cum_on(k if want_ndcg else 1, logits.device)
+        mean, _rows, dl, nd = load().node_loss_ndcg(logits, y, cum, int(k) if want_ndcg else 1, True, need_grad,
+                                                    want_ndcg)
+        if need_grad:
+            ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(nd)
+        return mean, nd
+
+    @staticmethod
+    def backward(ctx, g, _gnd):
+        (dl,) = ctx.saved_tensors
+        if float(g) != 1.0:            # (loss.backward() passes 1: the saved dlogits are the gradient as they are)
+            dl = dl * g
+        return dl, None, None
+
+
+def soft_cross_entropy(logits, y):
+    """Mean over rows of the soft-target cross-entropy of logits [M, C] against dense targets y [M, C] (>= 0, any row
+    sum): torch.nn.functional.cross_entropy(logits, y) with probability targets, from the row kernel
+    (tgnx_node_loss_ndcg).  The forward already wrote dlogits (scaled by 1 / M); backward returns them, multiplied by
+    the incoming gradient only when that is not 1.  y is data: no gradient.  An empty batch gives 0."""
+    return _NodeLoss.apply(logits.contiguous(), y.contiguous(), None)[0]
+
+
+@torch.no_grad()
+def ndcg_at_k(logits, y, k=10):
+    """NDCG@k of every row, float64 [M]: sklearn's ndcg_score(y, logits, k=k) with its tie averaging (tied scores
+    share the mean discount of the ranks they span), 0 for a row without a positive target.  No autograd."""
+    return load().node_loss_ndcg(logits.detach().contiguous(), y.contiguous(), _cum_on(k, logits.device), int(k),
+                                 False, False, True)[3]
+
+
+def node_loss_ndcg(logits, y, k=10):
+    """(soft_cross_entropy(logits, y), ndcg_at_k(logits, y, k)) from ONE pass of the row kernel over the logits (the
+    mean of the row losses is a second, one-workgroup launch): what the train_node / test_node loops call.  The loss
+    carries autograd as soft_cross_entropy's; the NDCG rows do not."""
+    return _NodeLoss.apply(logits.contiguous(), y.contiguous(), int(k))
