@@ -91,3 +91,37 @@ def test_tgn_param_layout_refuses_widths_outside_the_domain():
         for (a0, a1, name), (b0, _, _) in zip(blocks, blocks[1:]):
             assert a1 <= b0, (D, name)                                     # no two tensors overlap
         assert all(a % 4 == 0 for a, _, _ in blocks), (D, blocks)          # every block starts 16-byte aligned
+
+
+def test_tgnn_param_layout_refuses_widths_outside_the_domain():
+    """The TGNN step's check_cfg accepts mem_dim in [1, 128], msg_dim >= 0 with msg_dim + mem_dim <= 320 and 8 heads;
+    tgnx_tgnn_param_layout (offsets only: no device) refuses the rest with its message and afterwards lays the
+    domain's corners out as tgnx.model.param_shapes says.  tests/test_gpu_tgnn_widths.py compares the accepted
+    widths with the oracle."""
+    from tgnx import _lib
+    from tgnx.model import PARAM_ORDER, TgnnConfig, param_shapes
+    L = _lib.lib()
+
+    def layout(D, d, heads=8):
+        cfg = TgnnConfig(num_nodes=300, ring=10, mem_dim=D, msg_dim=d, heads=heads, max_batch=150, max_neg=8,
+                         feat_drop=0.0, attn_drop=0.0, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8)
+        off = (ctypes.c_int64 * (len(PARAM_ORDER) + 1))()
+        return L.tgnx_tgnn_param_layout(ctypes.byref(cfg), off), list(off)
+
+    for D, d, heads, msg in ((0, 16, 8, b"tgnn: mem_dim must be in [1, 128]"),
+                             (129, 16, 8, b"tgnn: mem_dim must be in [1, 128]"),
+                             (100, -1, 8, b"tgnn: msg_dim + mem_dim must be <= 320"),
+                             (128, 193, 8, b"tgnn: msg_dim + mem_dim must be <= 320"),
+                             (100, 16, 4, b"tgnn: heads must be 8")):
+        rc, _ = layout(D, d, heads)
+        assert rc == -1, (D, d, heads)                                     # TGNX_EINVAL
+        assert msg in L.tgnx_last_error(), (D, d, heads, L.tgnx_last_error())
+    for D, d in ((1, 0), (1, 319), (3, 0), (128, 0), (128, 192)):          # the domain's corners, after the refusals
+        rc, off = layout(D, d)
+        assert rc == 0, (D, d)
+        shapes = param_shapes(D, d, 8)
+        blocks = sorted((o, o + int(np.prod(shapes[name])), name) for name, o in zip(PARAM_ORDER, off))
+        assert blocks[0][0] == 0 and blocks[-1][1] <= off[-1], (D, d, blocks, off[-1])
+        for (a0, a1, name), (b0, _, _) in zip(blocks, blocks[1:]):
+            assert a1 <= b0, (D, d, name)                                  # no two tensors overlap
+        assert all(a % 4 == 0 for a, _, _ in blocks), (D, d, blocks)       # every block starts 16-byte aligned

@@ -8,7 +8,7 @@ fp32 cancellation floor (1e-3 of the tensor max), else within ~2 lr per step; ri
 import numpy as np
 import pytest
 
-from parity_harness import Pair, rel_err
+from parity_harness import Pair, _segment_sizes, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -90,19 +90,6 @@ def test_multi_step_trajectory_small_time_scale():
     assert max(well.values()) < 1e-5, well
     r = p.eval_step()
     assert abs(r["mrr"] - r["ref_mrr"]) < 5e-3
-
-
-def _segment_sizes(p):
-    """In-edge counts of the next batch's source / destination segments, from the oracle's ring and the batch's
-    blocks: valid ring entries + the self loop + the root's touches in earlier blocks of the batch."""
-    sl = slice(p.pos, p.pos + p.B)
-    src, dst, blk = p.s.src[sl], p.s.dst[sl], p.blk[sl]
-    valid = (p.ref_loader.e_id >= 0).sum(1)
-    sizes = []
-    for roots in (src, dst):
-        for r, b in zip(roots, blk):
-            sizes.append(valid[r] + 1 + int((((src == r) | (dst == r)) & (blk < b)).sum()))
-    return np.asarray(sizes)
 
 
 @pytest.mark.parametrize("K", [1, 9, 32])

@@ -1169,13 +1169,18 @@ __device__ void seg_bwd_body(const Ctx& c, const int bid, const int nblk) {
   for (int k = 0; k < KD; ++k) aUr[k] = 0.f;
   for (int w = bid * 4 + wv; w < S; w += nblk * 4) {
     const float g = c.seg_g[w];
-    if (g == 0.f) continue;
+    const int e0 = c.seg_eoff[w], ne = c.seg_eoff[w + 1] - e0;
+    if (g == 0.f) {  // (every ReLU of the predictor row dead: common at small D.)  tgnn_edge_bwd reads the dx of every
+      // edge, so the segment's rows are zeroed: left alone they would still hold an earlier step's values
+      float* __restrict__ DXz = c.DX + (int64_t)e0 * H;
+      for (int x = lane; x < ne * H; x += WAVE) DXz[x] = 0.f;
+      continue;
+    }
     Seg s;
     seg_of(c, w, lo, hi, start, s);
     const float gh = g * (1.0f / H);
     const float* sp = c.seg_stats + (int64_t)w * 4 * H;
     const float m = sp[h], l = sp[H + h], ft = sp[2 * H + h], er = sp[3 * H + h];
-    const int e0 = c.seg_eoff[w], ne = c.seg_eoff[w + 1] - e0;
     const uint64_t sk = seg_key(s.blk, s.root);
     float der = 0.f;
     if (ne > SEG_WIDE) {  // (wave-uniform) lane = edge slot, all heads per lane (as tgnn_seg_fwd's long segments)
@@ -1406,9 +1411,11 @@ __global__ void __launch_bounds__(64 * NW) tgnn_edge_bwd(Ctx c) {
 
 template <int CF, int CT, bool DROP, int NW>
 static void launch_edge_bwd_nw(const Ctx& c, hipStream_t s) {
+  // the largest slab check_cfg admits, mem_dim = DMAX with msg_dim + mem_dim = FMAX: 8 rows of 4,888 floats =
+  // 156,416 bytes, which with Uenc's 4 KB is 160,512 of the CU's 163,840 (a flat 150 KB is less than that launch asks for)
   static bool attr = [] {
     (void)hipFuncSetAttribute((const void*)tgnn_edge_bwd<CF, CT, DROP, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              150 * 1024);
+                              bwd_bufs(NW) * make_play(DMAX, FMAX - DMAX).total * 4);
     return true;
   }();
   (void)attr;
@@ -2427,8 +2434,9 @@ static int train_fwd_bwd_impl(const tgnx_tgnn_config* cfg, const tgnx_tgnn_buffe
     c.defer = adv->defer;
     c.apply_nel = grid_for(2 * c.D + (c.L.total - c.L.Ws), 1024);
   }
-  TGNX_CHECK_ARG(buf->neg && buf->grads && buf->out_pos && buf->out_neg && buf->feat && buf->ev_msg && buf->memory &&
-                     buf->time_assoc && buf->nbr && buf->eid && buf->rt,
+  // (msg_dim 0: the feature table and the batch's messages have no bytes, and CF = 0 reads none)
+  TGNX_CHECK_ARG(buf->neg && buf->grads && buf->out_pos && buf->out_neg && (c.d == 0 || (buf->feat && buf->ev_msg)) &&
+                     buf->memory && buf->time_assoc && buf->nbr && buf->eid && buf->rt,
                  "tgnx_tgnn_train_fwd_bwd: null buffer");
   TGNX_CHECK_ARG(!gen_neg || (buf->dst_nodes && buf->n_dst > 0), "tgnx_tgnn_train_fwd_bwd: no destination set");
   c.drop = dropout && (c.pf > 0.f || c.pa > 0.f);
@@ -2479,7 +2487,8 @@ int tgnx_tgnn_eval_step(const tgnx_tgnn_config* cfg, const tgnx_tgnn_buffers* bu
   TGNX_CHECK_ARG(Kn >= 1 && Kn <= cfg->max_neg, "tgnx_tgnn_eval_step: Kn must be in [1, max_neg]");
   int rc = make_ctx(cfg, buf, Kn, c);
   if (rc) return rc;
-  TGNX_CHECK_ARG(buf->neg && buf->out_pos && buf->out_neg && buf->mrr && buf->feat && buf->ev_msg && buf->memory,
+  TGNX_CHECK_ARG(buf->neg && buf->out_pos && buf->out_neg && buf->mrr && (c.d == 0 || (buf->feat && buf->ev_msg)) &&
+                     buf->memory,
                  "tgnx_tgnn_eval_step: null buffer");
   c.quirk = tile_quirk ? 1 : 0;
   c.drop = 0;
