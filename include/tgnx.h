@@ -327,6 +327,73 @@ int tgnx_negs_hist_rnd(const int64_t* src, const int64_t* dst, const void* t, in
                        const int64_t* pool, int64_t n_pool, uint64_t seed, int64_t max_draws, int64_t* out,
                        int32_t* k_hist, int64_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- live pair set (csrc/tgnx_pairset.hip)
+ * "Has this source ever interacted with this destination?" for a process that ingests events and retires their
+ * rows: an open-addressing hash table of (source, destination) pairs in device memory, updated by one launch per
+ * ingested batch.  It names no event rows, so compaction cannot invalidate it (DESIGN §3b-14 has the contract,
+ * tests/pairset_ref.py restates it as a dict).
+ *
+ * table: one device allocation of tgnx_pairset_bytes(capacity) = 20 * capacity bytes, 8-byte aligned; capacity is a
+ * power of two >= 64 (else 0 bytes / TGNX_EINVAL):
+ *   key     uint64[capacity]  (uint64)src << 32 | dst; the all-ones word is EMPTY
+ *   count   uint32[capacity]  occurrences                                             (identity 0)
+ *   t_first uint32[capacity]  the smallest stamp as an order-preserving uint32        (identity 0xFFFFFFFF)
+ *   t_last  uint32[capacity]  the largest stamp, likewise                             (identity 0)
+ * Stamps are the event table's float32 values: bits b (-0.0 taken as 0.0) are stored as ~b when the sign bit is set,
+ * else b | 0x80000000, so unsigned integer order is float order and min / max are integer atomics.
+ * Home slot = (key * 0x9E3779B97F4A7C15) >> (64 - log2(capacity)) in 64-bit unsigned arithmetic; probing is linear
+ * and wraps.  num_nodes must lie in [1, 2^32 - 1] (ids < 2^32 - 1, so no pair is the EMPTY word): TGNX_EINVAL.
+ *
+ * Every update of a present key is a commutative integer atomic and the value fields hold their identities before
+ * a key is published, so the contents are a function of the multiset of inserted events; the slot layout is not,
+ * and no output depends on it (tgnx_pairset_export's row order aside: sort by key).  Every loop is bounded: a probe
+ * visits at most `capacity` slots, the claim is one 64-bit compare-and-swap per visited slot, and an event that
+ * finds no slot is counted and dropped.  No entry point allocates or synchronises with the host.
+ *
+ * status (device int64[3], zeroed by the caller, accumulated by the kernels): [0] n_keys — keys claimed; [1]
+ * n_invalid — events with an id outside [0, num_nodes) or a NaN stamp (never used, never inserted); [2] n_overflow —
+ * events that found neither their key nor an EMPTY slot (the table was full; the caller's growth rule prevents it). */
+size_t tgnx_pairset_bytes(int64_t capacity);
+/* EMPTY keys and the value identities in every slot. */
+int tgnx_pairset_init(void* table, int64_t capacity, void* stream);
+/* One thread per event (src[i], dst[i], t[i]): claim or find the slot, count += 1, t_first = min, t_last = max. */
+int tgnx_pairset_insert(void* table, int64_t capacity, const int64_t* src, const int64_t* dst, const float* t, int64_t n,
+                        int64_t num_nodes, int64_t* status, void* stream);
+/* tgnx_pairset_insert with given values (tgnx_pairset_export's rows): count[i] in [1, 2^32) is added, t_first[i] /
+ * t_last[i] taken with min / max; anything else is counted in n_invalid. */
+int tgnx_pairset_import(void* table, int64_t capacity, const int64_t* keys, const int64_t* count, const float* t_first,
+                        const float* t_last, int64_t n, int64_t num_nodes, int64_t* status, void* stream);
+/* Per query i: out_seen[i] (one byte) = present && t_last >= cut, cut = since[i], or since_all when since is NULL
+ * (-inf: no cut; a NaN cut sees nothing); out_count / out_t_first / out_t_last of the pair whatever the cut, and
+ * 0 / +inf / -inf for an absent pair.  Any output may be NULL.  An id outside [0, num_nodes) is absent. */
+int tgnx_pairset_lookup(const void* table, int64_t capacity, int64_t num_nodes, const int64_t* src, const int64_t* dst,
+                        int64_t n, const float* since, float since_all, uint8_t* out_seen, int64_t* out_count,
+                        float* out_t_first, float* out_t_last, void* stream);
+/* For every source src[q] the candidates it has met (seen as above; since has Q entries or is NULL), as a ragged
+ * (out_ptr int64[Q + 1], out_ids): node ids in candidate order, duplicated candidates kept — the form the link
+ * operators take as `exclude`.  Two calls share one workspace: _count fills out_ptr (blocks of one source x 1,024
+ * candidates count their hits, one scan), the caller sizes out_ids from out_ptr[Q], _fill with the same arguments
+ * writes each block's hits at its offset by ballot / prefix compaction: no cursor, no [Q, C] intermediate, the
+ * output bit-identical for every run and grid.  Entries at or beyond out_cap are not written.  Q * ceil(C / 1024)
+ * must stay below 2^31 - 1 (0 bytes / TGNX_EINVAL). */
+size_t tgnx_pairset_select_ws_bytes(int64_t Q, int64_t C);
+int tgnx_pairset_select_count(const void* table, int64_t capacity, int64_t num_nodes, const int64_t* src, int64_t Q,
+                              const int64_t* cand, int64_t C, const float* since, float since_all, int64_t* out_ptr,
+                              void* ws, size_t ws_bytes, void* stream);
+int tgnx_pairset_select_fill(const void* table, int64_t capacity, int64_t num_nodes, const int64_t* src, int64_t Q,
+                             const int64_t* cand, int64_t C, const float* since, float since_all, int64_t* out_ids,
+                             int64_t out_cap, const void* ws, size_t ws_bytes, void* stream);
+/* Every live entry of old_table goes into new_table (initialised, any capacity) with its values, except those whose
+ * source or destination is flagged in drop_flags (uint8[num_nodes], NULL: none): growth and forgetting in one
+ * kernel.  status[0] is set to the new n_keys; status[2] counts entries that did not fit. */
+int tgnx_pairset_rehash(const void* old_table, int64_t old_capacity, void* new_table, int64_t new_capacity,
+                        const uint8_t* drop_flags, int64_t num_nodes, int64_t* status, void* stream);
+/* The live entries, compacted in no particular order: keys (src << 32 | dst), counts, decoded stamps; *out_n
+ * (device) = their number.  Rows at or beyond max_out are counted, not written.  The caller sorts by key: the
+ * sorted form is the checkpoint. */
+int tgnx_pairset_export(const void* table, int64_t capacity, int64_t* out_keys, int64_t* out_count, float* out_t_first,
+                        float* out_t_last, int64_t max_out, int64_t* out_n, void* stream);
+
 /* ---------------------------------------------------------------- TGN memory path
  * SURVEY §8 a14–a16 (the PyG TGN of the reference modules/ directory, wired as pyg_model_utils.py:10-36):
  * TGNMemory (modules/memory_module.py:25-215) with IdentityMessage (msg_func.py:12-18) and

@@ -14,6 +14,9 @@
 //   pair_index_build / pair_index_contains / negs_hist_rnd
 //                                            the (source, destination) pair index and TGB's hist_rnd evaluation
 //                                            negatives drawn from it (csrc/tgnx_negs.hip; tgnx/tgb_negs.py)
+//   pairset_insert / pairset_lookup / pairset_select
+//                                            the live (source, destination) pair set (csrc/tgnx_pairset.hip;
+//                                            tgnx/pairset.py allocates the table and applies the growth rule)
 //   gemm_f32                                 the modules' Linear contractions on the MFMA GEMM
 //   msg_agg_last / msg_agg_mean              LastAggregator / MeanAggregator (modules/msg_agg.py:15-26)
 //   gru_update                               TGNMemory.memory_updater GRUCell / RNNCell (memory_module.py:70-78)
@@ -283,6 +286,96 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> negs_hist_rnd(const at::Tensor& s
                               ws.data_ptr(), nb, cur_stream()),
            "tgnx_negs_hist_rnd");
   return {out, k_hist, status};
+}
+
+// ---- live pair set (csrc/tgnx_pairset.hip; tgnx/pairset.py owns allocation and the growth rule).  table is the
+// int64 view of a tgnx_pairset_bytes(capacity) allocation: capacity = numel * 2 / 5.
+int64_t pairset_capacity(const at::Tensor& table) {
+  dev_tensor(table, at::kLong, "table");
+  const int64_t cap = table.numel() * 2 / 5;
+  TORCH_CHECK(cap >= 64 && (cap & (cap - 1)) == 0 && tgnx_pairset_bytes(cap) == (size_t)table.numel() * 8,
+              "table must be the int64 view of a pair set of a power-of-two capacity >= 64");
+  return cap;
+}
+
+const float* pairset_since(const at::Tensor& table, const c10::optional<at::Tensor>& since, int64_t n) {
+  if (!since.has_value()) return nullptr;
+  dev_tensor(*since, at::kFloat, "since");
+  same_device(table, {&*since});
+  TORCH_CHECK(since->numel() == n, "one cut per query");
+  return since->data_ptr<float>();
+}
+
+// The op checks the chunk size only.  The caller owns the growth rule (tgnx/pairset.py: read status[0] on schedule,
+// rehash into a larger table before the load passes 1/2): an insert into a table that is too full does not fail, it
+// counts the events it had no slot for in status[2].
+void pairset_insert(at::Tensor table, at::Tensor status, const at::Tensor& src, const at::Tensor& dst,
+                    const at::Tensor& t, int64_t num_nodes) {
+  const int64_t cap = pairset_capacity(table);
+  dev_tensor(status, at::kLong, "status");
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(dst, at::kLong, "dst");
+  dev_tensor(t, at::kFloat, "t");
+  same_device(table, {&status, &src, &dst, &t});
+  const int64_t n = src.numel();
+  TORCH_CHECK(dst.numel() == n && t.numel() == n && status.numel() >= 3, "pairset_insert: shapes");
+  TORCH_CHECK(n <= cap / 8, "pairset_insert: at most capacity / 8 events per call (the growth rule's chunk)");
+  const c10::OptionalDeviceGuard guard(table.device());
+  check_rc(tgnx_pairset_insert(table.data_ptr(), cap, src.data_ptr<int64_t>(), dst.data_ptr<int64_t>(),
+                               t.data_ptr<float>(), n, num_nodes, status.data_ptr<int64_t>(), cur_stream()),
+           "tgnx_pairset_insert");
+}
+
+// (seen bool[n], count int64[n], t_first float32[n], t_last float32[n])
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> pairset_lookup(const at::Tensor& table, const at::Tensor& src,
+                                                                          const at::Tensor& dst, int64_t num_nodes,
+                                                                          const c10::optional<at::Tensor>& since,
+                                                                          c10::optional<double> since_all) {
+  const int64_t cap = pairset_capacity(table);
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(dst, at::kLong, "dst");
+  same_device(table, {&src, &dst});
+  const int64_t n = src.numel();
+  TORCH_CHECK(dst.numel() == n, "pairset_lookup: shapes");
+  const float* ps = pairset_since(table, since, n);
+  const c10::OptionalDeviceGuard guard(table.device());
+  at::Tensor seen = at::empty({n}, src.options().dtype(at::kBool)), count = at::empty({n}, src.options());
+  at::Tensor tf = at::empty({n}, src.options().dtype(at::kFloat)), tl = at::empty({n}, src.options().dtype(at::kFloat));
+  check_rc(tgnx_pairset_lookup(table.data_ptr(), cap, num_nodes, src.data_ptr<int64_t>(), dst.data_ptr<int64_t>(), n, ps,
+                               since_all.has_value() ? (float)*since_all : -INFINITY,
+                               reinterpret_cast<uint8_t*>(seen.data_ptr<bool>()), count.data_ptr<int64_t>(),
+                               tf.data_ptr<float>(), tl.data_ptr<float>(), cur_stream()),
+           "tgnx_pairset_lookup");
+  return {seen, count, tf, tl};
+}
+
+// (ptr int64[Q + 1], ids): one host read of ptr[Q] sizes the ids
+std::tuple<at::Tensor, at::Tensor> pairset_select(const at::Tensor& table, const at::Tensor& src, const at::Tensor& cand,
+                                                  int64_t num_nodes, const c10::optional<at::Tensor>& since,
+                                                  c10::optional<double> since_all) {
+  const int64_t cap = pairset_capacity(table);
+  dev_tensor(src, at::kLong, "src");
+  dev_tensor(cand, at::kLong, "cand");
+  same_device(table, {&src, &cand});
+  const int64_t Q = src.numel(), C = cand.numel();
+  const float* ps = pairset_since(table, since, Q);
+  const float cut = since_all.has_value() ? (float)*since_all : -INFINITY;
+  const c10::OptionalDeviceGuard guard(table.device());
+  const size_t nb = tgnx_pairset_select_ws_bytes(Q, C);
+  TORCH_CHECK(nb > 0, "pairset_select: Q x C beyond one call");
+  at::Tensor ws = at::empty({(int64_t)nb}, src.options().dtype(at::kByte));
+  at::Tensor ptr = at::empty({Q + 1}, src.options());
+  check_rc(tgnx_pairset_select_count(table.data_ptr(), cap, num_nodes, src.data_ptr<int64_t>(), Q,
+                                     cand.data_ptr<int64_t>(), C, ps, cut, ptr.data_ptr<int64_t>(), ws.data_ptr(), nb,
+                                     cur_stream()),
+           "tgnx_pairset_select_count");
+  const int64_t total = ptr[Q].item<int64_t>();
+  at::Tensor ids = at::empty({total}, src.options());
+  check_rc(tgnx_pairset_select_fill(table.data_ptr(), cap, num_nodes, src.data_ptr<int64_t>(), Q,
+                                    cand.data_ptr<int64_t>(), C, ps, cut, ids.data_ptr<int64_t>(), total, ws.data_ptr(),
+                                    nb, cur_stream()),
+           "tgnx_pairset_select_fill");
+  return {ptr, ids};
 }
 
 at::Tensor gemm_f32(const at::Tensor& A, const at::Tensor& B, const c10::optional<at::Tensor>& bias, bool trans_a,
@@ -1125,6 +1218,14 @@ TORCH_LIBRARY(tgnx, m) {
   m.def("negs_hist_rnd(Tensor src, Tensor dst, Tensor t, int lo, int hi, int k, int q, int hist_hi, Tensor indptr, "
         "Tensor indices, Tensor first, Tensor pool, int seed=0, int max_draws=0) -> (Tensor, Tensor, Tensor)",
         &negs_hist_rnd);
+  m.def("pairset_insert(Tensor(a!) table, Tensor(b!) status, Tensor src, Tensor dst, Tensor t, int num_nodes) -> ()",
+        &pairset_insert);
+  m.def("pairset_lookup(Tensor table, Tensor src, Tensor dst, int num_nodes, Tensor? since=None, float? since_all=None) "
+        "-> (Tensor, Tensor, Tensor, Tensor)",
+        &pairset_lookup);
+  m.def("pairset_select(Tensor table, Tensor src, Tensor cand, int num_nodes, Tensor? since=None, float? since_all=None) "
+        "-> (Tensor, Tensor)",
+        &pairset_select);
   m.def("gemm_f32(Tensor A, Tensor B, Tensor? bias=None, bool trans_a=False, bool trans_b=False) -> Tensor", &gemm_f32);
   // SURVEY §8b's names for the sampler ops (the same functions as ring_sample / ring_insert / ring_reset)
   m.def("sample_recent(Tensor nbr, Tensor e_id, Tensor t, Tensor(a!) assoc, Tensor n_id) -> "

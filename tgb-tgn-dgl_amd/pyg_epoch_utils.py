@@ -10,3 +10,4 @@ from tgnx.tgn_epoch import forget  # noqa: F401
 from tgnx.tgn_epoch import edgebank, tgb_negatives  # noqa: F401
 from tgnx.nodeprop import test_node, train_node  # noqa: F401
 from tgnx.nn import NodePredictor  # noqa: F401
+from tgnx.tgn_epoch import edgebank_stream, edgebank_window, enable_pair_history, seen  # noqa: F401

@@ -90,6 +90,19 @@ SIGNATURES = {
     "tgnx_negs_hist_rnd_ws_bytes": (c_sz, [c_i64, c_i64]),
     "tgnx_negs_hist_rnd": (ctypes.c_int, [P, P, P, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, P, P, P, c_i64,
                                           c_i64, P, c_i64, c_u64, c_i64, P, P, P, P, c_sz, c_vp]),
+    # live pair set (tgnx_pairset.hip)
+    "tgnx_pairset_bytes": (c_sz, [c_i64]),
+    "tgnx_pairset_init": (ctypes.c_int, [P, c_i64, c_vp]),
+    "tgnx_pairset_insert": (ctypes.c_int, [P, c_i64, P, P, P, c_i64, c_i64, P, c_vp]),
+    "tgnx_pairset_import": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i64, c_i64, P, c_vp]),
+    "tgnx_pairset_lookup": (ctypes.c_int, [P, c_i64, c_i64, P, P, c_i64, P, ctypes.c_float, P, P, P, P, c_vp]),
+    "tgnx_pairset_select_ws_bytes": (c_sz, [c_i64, c_i64]),
+    "tgnx_pairset_select_count": (ctypes.c_int, [P, c_i64, c_i64, P, c_i64, P, c_i64, P, ctypes.c_float, P, P, c_sz,
+                                                 c_vp]),
+    "tgnx_pairset_select_fill": (ctypes.c_int, [P, c_i64, c_i64, P, c_i64, P, c_i64, P, ctypes.c_float, P, c_i64, P,
+                                                c_sz, c_vp]),
+    "tgnx_pairset_rehash": (ctypes.c_int, [P, c_i64, P, c_i64, P, c_i64, P, c_vp]),
+    "tgnx_pairset_export": (ctypes.c_int, [P, c_i64, P, P, P, P, c_i64, P, c_vp]),
     "tgnx_gemm_f32_ws_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "tgnx_gemm_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i64, c_i32, P, c_i64, c_i32, P, c_i64, P, c_i32, P, c_sz,
                                      c_vp]),

@@ -39,6 +39,7 @@ OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "t
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
        "memstore_put", "memstore_count", "memstore_gather", "memstore_build_msg",
        "pair_index_build", "pair_index_contains", "negs_hist_rnd",
+       "pairset_insert", "pairset_lookup", "pairset_select",
        "node_predictor", "node_predictor_bwd", "node_loss_ndcg")
 _loaded = False
 

@@ -700,6 +700,9 @@ class TgnEngine:
         self._emb_tab = None
         self._emb_all = True
         self._emb_ver = None
+        # the live pair history (enable_pair_history; off by default): a tgnx.pairset.PairSet that observe / eval
+        # batches record into with one more launch
+        self._pairs = None
         if optimizer is None:
             self.adam_m, self.adam_v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
         else:
@@ -793,6 +796,8 @@ class TgnEngine:
         b = self._buffers(0)
         _lib.call("tgnx_tgn_reset_state", ctypes.byref(self.cfg), ctypes.byref(b), self._stream())
         self.loader.reset_state()
+        if self._pairs is not None:       # (the stream starts over: its rows will be observed again)
+            self._pairs.clear()
 
     def flush(self):
         """TGNMemory.train(False) (memory_module.py:209-215)."""
@@ -860,6 +865,7 @@ class TgnEngine:
         b = self._buffers(negs.data_ptr() - start * Kn * 8)
         _lib.call("tgnx_tgn_eval_step", ctypes.byref(self.cfg), ctypes.byref(b), Kn, self._stream())
         self._emb_touch(start, B)
+        self._pairs_touch(start, B)
         self._keep = negs
         return self.out_pos[:B], self.out_neg[:B * Kn].view(B, Kn), self.mrr[:B]
 
@@ -1054,6 +1060,7 @@ class TgnEngine:
         b.xrows, b.xcap = 0, 0
         _lib.call("tgnx_tgn_observe_step", ctypes.byref(self.cfg), ctypes.byref(b), self._stream())
         self._emb_touch(start, B)
+        self._pairs_touch(start, B)
 
     def observe_range(self, lo: int, hi: int, batch=None):
         """observe() over resident rows [lo, hi) in batches of `batch` (default cfg.max_batch), the last one partial:
@@ -1233,7 +1240,9 @@ class TgnEngine:
 
         Returns {"nodes": distinct ids, "ring_slots": slots removed from other nodes' rows, "ring_rows": rows that
         lost one, "store_entries": entries dropped from other nodes' runs}, and "kept" (compact_events' result) with
-        compact=True.  An empty id list is a no-op: zeros, nothing launched, compacted or dropped.
+        compact=True.  With the pair history enabled (enable_pair_history) every pair that names a forgotten node is
+        erased as well and "pairs" counts them (three more host reads); the key is absent otherwise.  An empty id list
+        is a no-op: zeros, nothing launched, compacted or dropped.
 
         Like compact_events, everything that captured a pointer or names a batch prepared from the old state is
         dropped — the captured train and eval graphs, the plan table, the resident train and eval bindings (not made
@@ -1245,7 +1254,7 @@ class TgnEngine:
         device only (ValueError at world > 1 / the data-parallel forms).  One host read (two on the error path)."""
         ids = self._ids(ids)
         if not check_forget_args(self.cfg.num_nodes, ids.numel(), self.world, self.dp):
-            return dict.fromkeys(FORGET_COUNTS, 0)
+            return dict.fromkeys(FORGET_COUNTS + (("pairs",) if self._pairs is not None else ()), 0)
         self._settle()
         N = int(self.cfg.num_nodes)
         ws, rec = self._forget_plan(ids)
@@ -1264,6 +1273,8 @@ class TgnEngine:
         if pool is not None:
             self.dst_nodes = pool
         out = {k: int(rec[i]) for i, k in enumerate(FORGET_COUNTS)}
+        if self._pairs is not None:       # every pair that names a forgotten node (tgnx_pairset_rehash with flags)
+            out["pairs"] = self._pair_set("forget_nodes").erase_nodes(ids)
         if compact:
             out["kept"] = self.compact_events()
         return out
@@ -1292,8 +1303,9 @@ class TgnEngine:
         """Make a stream_state() dict this engine's stream state, whatever table the engine was built over (one row
         is enough).  format, the fingerprint, the shapes and ERR == 0 in the saved ctl are checked first: ValueError
         before anything is written.  Table and store are sized by reserve_events, everything is copied in,
-        loader.cur_e_id = num_events, and bindings and graphs are dropped as compact_events drops them.  A state of
-        another node count: load_stream_state_grow()."""
+        loader.cur_e_id = num_events, and bindings and graphs are dropped as compact_events drops them.  Keys beyond
+        STREAM_STATE_KEYS (a save_stream file's "pair_history") are ignored.  A state of another node count:
+        load_stream_state_grow()."""
         self._load_stream_state(state, False)
 
     @torch.no_grad()
@@ -1583,12 +1595,18 @@ class TgnEngine:
         q = torch.arange(ptr.numel() - 1, device=self.dev)
         return torch.repeat_interleave(q, ptr[1:] - ptr[:-1], output_size=nnz)
 
-    def _exclusions(self, src, exclude_seen, exclude):
+    def _exclusions(self, src, exclude_seen, exclude, history=None):
         """(ptr [Q + 1], keys) of the per-source exclusions, each segment ascending: the valid entries of the source's
-        neighbour-ring row (e_id >= 0; reset_state leaves stale ids in `neighbors`) and the caller's lists.  Invalid
-        ring slots become the key N, which no node carries.  Device ops only; None when nothing is excluded."""
+        neighbour-ring row (e_id >= 0; reset_state leaves stale ids in `neighbors`), the caller's lists and, with
+        history = (candidates, since), the candidates the pair history says the source has met (PairSet.select: one
+        host read for the length).  Invalid ring slots become the key N, which no node carries.  Device ops only
+        otherwise; None when nothing is excluded."""
         N, Q = self.cfg.num_nodes, src.numel()
         seg, key = [], []
+        if history is not None:
+            ptr, ids = self._pair_set("exclude_history=True").select(src, history[0], history[1])
+            key.append(ids)
+            seg.append(self._segments(ptr, ids.numel()))
         if exclude_seen:
             ld = self.loader
             rows = torch.where(ld.e_id[src] >= 0, ld.neighbors[src], torch.full_like(ld.neighbors[src], N))
@@ -1607,7 +1625,7 @@ class TgnEngine:
     @torch.no_grad()
     def recommend_filtered(self, src, k: int, candidates=None, return_scores: bool = False, *,
                            exclude_seen: bool = False, exclude_self: bool = False, exclude=None, per_source=None,
-                           cached: bool = False):
+                           cached: bool = False, exclude_history: bool = False, history_since=None):
         """recommend() with per-source exclusions and per-source candidate lists; read-only in the same way.
         exclude_seen: leave out the nodes in the source's neighbour-ring row (its most recent interaction partners).
         exclude_self: leave out the source itself.  exclude: more node ids per source, a (ptr, node_ids) tuple of
@@ -1618,14 +1636,22 @@ class TgnEngine:
         (ops.link_topk(lists=...)): equal logits by the entry's place in the list; excluded entries are masked in a
         private copy.  Returns (val [Q, k], node_ids [Q, k][, logits [nnz]]), the logits aligned with the caller's
         entries and NaN at an excluded one.  cached: the embeddings are rows of the embedding
-        table (recommend_cached())."""
+        table (recommend_cached()).
+        exclude_history (enable_pair_history() first, RuntimeError otherwise): leave out every candidate the source
+        has ever interacted with as a source — the whole recorded history, not the ring's last `ring` partners;
+        history_since: only pairs whose last interaction is at or after this stamp (a float, or one per source).  The
+        met candidates come from PairSet.select and are merged with the other exclusions; a per_source list is
+        filtered with PairSet.contains over its entries."""
         from . import ops
         src = self._ids(src)
         Q, N = src.numel(), self.cfg.num_nodes
         if Q and bool(((src < 0) | (src >= N)).any()):
             raise ValueError(f"recommend: node ids must be in [0, {N})")
         w = self._link_weights()
-        ex = self._exclusions(src, exclude_seen, exclude)
+        ps = self._pair_set("exclude_history=True") if exclude_history else None
+        # (the candidates are needed ahead of the exclusions only by the history's select)
+        cand = self._candidates(candidates) if ps is not None and per_source is None else None
+        ex = self._exclusions(src, exclude_seen, exclude, (cand, history_since) if cand is not None else None)
         if per_source is not None:
             if candidates is not None:
                 raise ValueError("recommend: per_source and candidates are mutually exclusive")
@@ -1640,12 +1666,18 @@ class TgnEngine:
                 comp = seg * (N + 1) + ids
                 at = torch.searchsorted(ex[2], comp).clamp(max=ex[2].numel() - 1)
                 pos[ex[2][at] == comp] = -1
+            if ps is not None and ids.numel():
+                since = history_since
+                if torch.is_tensor(since) or isinstance(since, np.ndarray):
+                    since = torch.as_tensor(since).to(self.dev, torch.float32).view(-1)[seg]
+                pos[ps.contains(src[seg], ids, since)] = -1
             out = ops.link_topk(zs, zu, *w, k, sigmoid=True, return_scores=return_scores, lists=(ptr, pos),
                                 validate=False, max_len=longest)
             return (out[0], self._node_ids(out[1], uniq)) + tuple(out[3:])
         if ex is None and not exclude_self:
             return self._recommend(src, k, candidates, return_scores, cached)
-        cand = self._candidates(candidates)
+        if cand is None:
+            cand = self._candidates(candidates)
         zs, zc = self._embed_lists([src, cand], cached, "recommend", 1 if self._all_nodes(candidates) else None)
         out = ops.link_topk(zs, zc, *w, k, sigmoid=True, return_scores=return_scores, cand_key=cand,
                             src_key=src if exclude_self else None, exclude=None if ex is None else ex[:2],
@@ -1678,7 +1710,8 @@ class TgnEngine:
 
     @torch.no_grad()
     def rank(self, src, dst, candidates=None, return_scores: bool = False, *, exclude_seen: bool = False,
-             exclude_self: bool = False, exclude=None, cached: bool = False):
+             exclude_self: bool = False, exclude=None, cached: bool = False, exclude_history: bool = False,
+             history_since=None):
         """Where the model places the destination that happened: for every pair (src[i], dst[i]) the rank of dst[i]
         among the candidates recommend() would choose from (default: the same), at the current stream state and
         with recommend_filtered()'s exclusions (the "filtered" setting: the true destination itself is never
@@ -1688,7 +1721,8 @@ class TgnEngine:
         A destination outside `candidates` is ranked against all of them.  src, the candidates and dst are embedded
         once with embed(); the counts come from one fused pass (ops.link_rank), no [Q, C] logits unless asked for.
         Read-only as recommend() is.  cached: src and the candidate + destination rows are gathered from the embedding
-        table (enable_embedding_table; refreshed first)."""
+        table (enable_embedding_table; refreshed first).  exclude_history / history_since: recommend_filtered()'s —
+        the candidates the pair history says the source has met do not compete (the true destination still does)."""
         from . import ops
         src, dst = self._ids(src), self._ids(dst)
         Q, N = src.numel(), self.cfg.num_nodes
@@ -1698,7 +1732,7 @@ class TgnEngine:
             raise ValueError(f"rank: node ids must be in [0, {N})")
         cand = self._candidates(candidates)
         C = cand.numel()
-        ex = self._exclusions(src, exclude_seen, exclude)
+        ex = self._exclusions(src, exclude_seen, exclude, (cand, history_since) if exclude_history else None)
         if cached:
             zs, zc = self._embed_lists([src, torch.cat([cand, dst])], True, "rank")
         else:
@@ -1714,14 +1748,16 @@ class TgnEngine:
         return out
 
     def rank_events(self, start: int, B: int, candidates=None, *, exclude_seen: bool = False,
-                    exclude_self: bool = False, exclude=None, cached: bool = False):
+                    exclude_self: bool = False, exclude=None, cached: bool = False, exclude_history: bool = False,
+                    history_since=None):
         """One prequential step over resident rows [start, start + B): rank() of src[e] -> dst[e] at the state before
         them, then observe(start, B).  Returns rank()'s tuple.  cached: rank(cached=True) — each step then embeds only
         the rows the previous step's batch made stale."""
         start, B = int(start), int(B)
         check_observe_args(start, B, self.cfg.max_batch, self.num_events, self.world)
         out = self.rank(self._tab[0][start:start + B], self._tab[1][start:start + B], candidates,
-                        exclude_seen=exclude_seen, exclude_self=exclude_self, exclude=exclude, cached=cached)
+                        exclude_seen=exclude_seen, exclude_self=exclude_self, exclude=exclude, cached=cached,
+                        exclude_history=exclude_history, history_since=history_since)
         self.observe(start, B)
         return out
 
@@ -1739,7 +1775,8 @@ class TgnEngine:
         (recommend_filtered()'s forms); exclusion is by node id, so every position of a duplicated candidate goes.
         k beyond the candidates left pads with node id -1 and score -inf.  cached: the embeddings are rows of the
         embedding table (enable_embedding_table; refreshed first), and with the default candidates the table itself
-        is the candidate operand, with no gather.  Read-only as recommend() is.  One device only."""
+        is the candidate operand, with no gather.  Read-only as recommend() is.  One device only.  (To leave out what
+        the pair history says a query node has met, pass exclude=history_exclusions(nodes, candidates).)"""
         from . import ops
         if self.world > 1:
             raise ValueError("similar: one device only (world > 1 is not built)")
@@ -1755,6 +1792,86 @@ class TgnEngine:
                             q_key=nodes if exclude_self else None, exclude=None if ex is None else ex[:2],
                             validate=False)
         return (out[0], self._node_ids(out[1], cand)) + tuple(out[2:])
+
+    # ------------------------------------------------------------------ the live pair history
+    def enable_pair_history(self, capacity=None) -> None:
+        """Keep a live index of the (source, destination) pairs the stream has shown (off by default): a
+        tgnx.pairset.PairSet on the device that every observe() / eval_batch() — and so observe_range, observe_events
+        and rank_events — records its batch into with one more launch (tgnx_pairset_insert) after the step.  It holds
+        counts and first / last stamps, no event rows, so compact_events() leaves it valid; grow_nodes only moves its
+        id bound; forget_nodes erases the pairs that name a forgotten node; reset_state() empties it.  The resident
+        eval pass and the train steps take their rows from a device cursor and do not record: record_pairs(lo, hi)
+        does it for them.  capacity: initial slots (default and minimum: next_pow2(8 * max_batch), so a batch is one
+        launch); it doubles by PairSet's rule, which reads the host once per capacity / 8 recorded events at most.
+        Enabling twice keeps the history.  load_stream_state() does not touch it: pair_history_state() /
+        load_pair_history_state() are its checkpoint (the drop-in save_stream / load_stream carry both).  One device
+        only (ValueError at world > 1 / dp)."""
+        from . import pairset
+        if self.world > 1 or self.dp:
+            raise ValueError("enable_pair_history: one device only (world > 1 is not built)")
+        if self._pairs is None:
+            cap = pairset.min_capacity(self.cfg.max_batch)
+            if capacity is not None:
+                cap = max(cap, pairset.check_capacity(capacity))
+            self._pairs = pairset.PairSet(int(self.cfg.num_nodes), cap, device=self.dev)
+
+    def disable_pair_history(self) -> None:
+        """Free the history; every call issues exactly the launches it issues without the feature."""
+        self._pairs = None
+
+    def _pair_set(self, what: str):
+        """The PairSet with its id bound at cfg.num_nodes, or RuntimeError naming enable_pair_history()."""
+        ps = self._pairs
+        if ps is None:
+            raise RuntimeError(f"{what} needs the pair history: call enable_pair_history() first")
+        if ps.num_nodes != int(self.cfg.num_nodes):
+            ps.set_num_nodes(int(self.cfg.num_nodes))
+        return ps
+
+    def _pairs_touch(self, start: int, B: int) -> None:
+        """Record event rows [start, start + B) in the pair history (nothing to do while it is off)."""
+        if self._pairs is None or B <= 0:
+            return
+        tab = self._tab
+        self._pair_set("record").insert_ptr(tab[0].data_ptr() + start * 8, tab[1].data_ptr() + start * 8,
+                                            tab[2].data_ptr() + start * 4, B)
+
+    def record_pairs(self, lo: int, hi: int) -> None:
+        """Record resident rows [lo, hi) in the pair history without touching the stream state: for callers who
+        trained or validated over them with the resident passes, which do not record."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.num_events:
+            raise ValueError(f"record_pairs: rows [{lo}, {hi}) outside the event table ({self.num_events} events)")
+        self._pair_set("record_pairs")
+        self._pairs_touch(lo, hi - lo)
+
+    def clear_pair_history(self) -> None:
+        """Empty the pair history (its capacity stays)."""
+        self._pair_set("clear_pair_history").clear()
+
+    def seen(self, src, dst, since=None) -> torch.Tensor:
+        """bool[n] on the device: has src[i] ever interacted with dst[i] (as source and destination, in the recorded
+        batches) — with `since` (a float or one per query), at or after that stamp.  No host read."""
+        return self._pair_set("seen").contains(src, dst, since)
+
+    def pair_stats(self, src, dst):
+        """(count int64[n], t_first float32[n], t_last float32[n]) of the pairs: 0 / +inf / -inf for one never seen."""
+        return self._pair_set("pair_stats").lookup(src, dst)[1:]
+
+    def history_exclusions(self, src, candidates=None, since=None):
+        """(ptr int64[Q + 1], node ids) on the device: for every source the candidates (default: recommend()'s) the
+        pair history says it has met (at or after `since`), in candidate order — PairSet.select, the list that
+        exclude_history=True merges, in the form every query takes as exclude=.  One host read."""
+        return self._pair_set("history_exclusions").select(self._ids(src), self._candidates(candidates), since)
+
+    def pair_history_state(self) -> dict:
+        """PairSet.state() of the history: the pairs sorted by key with counts and stamps (a checkpoint)."""
+        return self._pair_set("pair_history_state").state()
+
+    def load_pair_history_state(self, state: dict) -> None:
+        """Replace the history by a pair_history_state() dict's (enabled here if it is not)."""
+        self.enable_pair_history()
+        self._pair_set("load_pair_history_state").load_state(state)
 
     # ------------------------------------------------------------------ hist_rnd evaluation negatives
     def pair_history(self):

@@ -213,12 +213,13 @@ def recommend(model, neighbor_loader, src, k, candidates=None):
 
 @torch.no_grad()
 def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclude_seen=False, exclude_self=False,
-                       exclude=None, per_source=None, cached=False):
+                       exclude=None, per_source=None, cached=False, exclude_history=False, history_since=None):
     """recommend() with per-source exclusions (exclude_seen: the source's recent interaction partners; exclude_self;
     exclude: more node ids per source) or a candidate list per source (per_source), TgnEngine.recommend_filtered's
     keywords passed through.  cached: read the engine's embedding table (enabled here if it is not) instead of
-    embedding the sources and candidates again; without exclusions this is recommend() from the table.  Read-only;
-    switches the memory to eval first as recommend() does."""
+    embedding the sources and candidates again; without exclusions this is recommend() from the table.
+    exclude_history / history_since: leave out everything the source has ever met (enable_pair_history() first).
+    Read-only; switches the memory to eval first as recommend() does."""
     eng = getattr(_owner(model), "_tgnx_engine", None)
     if eng is None or eng.loader is not neighbor_loader:
         raise RuntimeError("tgnx recommend_filtered: no engine bound to this model / neighbor_loader yet (run train() "
@@ -229,7 +230,8 @@ def recommend_filtered(model, neighbor_loader, src, k, candidates=None, *, exclu
     if cached:
         eng.enable_embedding_table()
     return eng.recommend_filtered(src, k, candidates=candidates, exclude_seen=exclude_seen, exclude_self=exclude_self,
-                                  exclude=exclude, per_source=per_source, cached=cached)
+                                  exclude=exclude, per_source=per_source, cached=cached,
+                                  exclude_history=exclude_history, history_since=history_since)
 
 
 @torch.no_grad()
@@ -252,7 +254,7 @@ def similar(model, neighbor_loader, nodes, k, candidates=None, *, metric="cosine
 
 @torch.no_grad()
 def rank_stream(model, neighbor_loader, lo, hi, batch, candidates=None, ks=(1, 10, 50), *, exclude_seen=False,
-                exclude_self=False, cached=False):
+                exclude_self=False, cached=False, exclude_history=False, history_since=None, split_history=False):
     """Prequential full-catalogue ranking over rows [lo, hi) of the event table of the engine train() / test()
     attached to the model: every batch of `batch` events is ranked at the state before it (TgnEngine.rank_events: the
     true destination against every candidate recommend() would choose from, recommend_filtered()'s exclusions), then
@@ -261,7 +263,13 @@ def rank_stream(model, neighbor_loader, lo, hi, batch, candidates=None, ks=(1, 1
     end.  Switches the memory to eval first as recommend() does.  cached: rank from the engine's embedding table
     (enabled here if it is not), so that each batch embeds only the rows the batch before it made stale instead of
     every candidate; ranks may differ from the uncached ones where two competing logits are closer than the
-    embeddings' tolerance."""
+    embeddings' tolerance.
+    exclude_history / history_since: TgnEngine.rank's (enable_pair_history() first).  split_history (the same
+    requirement): the result also carries "n_repeat" / "n_novel" (a positive is a repeat when the pair history held its
+    pair before its batch: one lookup per batch, ahead of the batch's recording), "mrr_repeat" / "mrr_novel" and
+    "hits@k_repeat" / "hits@k_novel", the means over each part (numpy's, over the ranks read back; NaN for an empty
+    part), and "repeat" (bool [hi - lo] on the device): the number that says whether the model beats memorisation.  The
+    other keys are computed exactly as without it."""
     eng = _bound_engine(model, neighbor_loader, "rank_stream")
     lo, hi, batch = int(lo), int(hi), int(batch)
     if not (0 <= lo <= hi <= eng.num_events) or not (0 < batch <= eng.cfg.max_batch):
@@ -272,13 +280,31 @@ def rank_stream(model, neighbor_loader, lo, hi, batch, candidates=None, ks=(1, 1
         eng._mode_train = False
     if cached:
         eng.enable_embedding_table()
-    ranks = [eng.rank_events(a, min(batch, hi - a), candidates, exclude_seen=exclude_seen,
-                             exclude_self=exclude_self, cached=cached)[0] for a in range(lo, hi, batch)]
+    if split_history:
+        eng._pair_set("rank_stream(split_history=True)")
+    ranks, reps = [], []
+    for a in range(lo, hi, batch):
+        b = min(batch, hi - a)
+        if split_history:                                    # (the bank as it stood before the batch)
+            reps.append(eng.seen(eng.src[a:a + b], eng.dst[a:a + b]))
+        ranks.append(eng.rank_events(a, b, candidates, exclude_seen=exclude_seen, exclude_self=exclude_self,
+                                     cached=cached, exclude_history=exclude_history, history_since=history_since)[0])
     rank = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.float64, device=eng.dev)
     stats = torch.stack([torch.nan_to_num(1.0 / rank, nan=0.0).sum()] + [(rank <= k).sum().double() for k in ks])
     stats = (stats / max(hi - lo, 1)).tolist()
     out = {"mrr": stats[0], "rank": rank}
     out.update({f"hits@{k}": v for k, v in zip(ks, stats[1:])})
+    if split_history:                                        # (the parts' means are numpy's over the ranks read back)
+        import numpy as np
+        rep = torch.cat(reps) if reps else torch.zeros(0, dtype=torch.bool, device=eng.dev)
+        out["repeat"] = rep
+        r_host, m_host = rank.cpu().numpy(), rep.cpu().numpy()
+        for name, m in (("repeat", m_host), ("novel", ~m_host)):
+            part = r_host[m]
+            n = int(part.size)
+            out[f"n_{name}"] = n
+            out[f"mrr_{name}"] = float(np.nan_to_num(1.0 / part, nan=0.0).mean()) if n else float("nan")
+            out.update({f"hits@{k}_{name}": (float((part <= k).mean()) if n else float("nan")) for k in ks})
     return out
 
 
@@ -426,23 +452,110 @@ def edgebank(loader, batch=None, device="cuda"):
                         loader.batch_size if batch is None else int(batch))
 
 
+def edgebank_window(t_train, ratio=0.15) -> float:
+    """The duration of EdgeBank-tw's window as TGB's default states it: `ratio` (0.15) of the span of the training
+    timestamps."""
+    t = torch.as_tensor(t_train).double()
+    if t.numel() == 0 or not 0.0 < ratio <= 1.0:
+        raise ValueError("edgebank_window: empty timestamps, or ratio outside (0, 1]")
+    return float((t.max() - t.min()) * ratio)
+
+
+@torch.no_grad()
+def edgebank_stream(loader, lo, hi, batch, negs, window=None, device="cuda"):
+    """Prequential EdgeBank over rows [lo, hi) of a stream from a live tgnx.pairset.PairSet: the bank is loaded with rows
+    [0, lo), then every batch of `batch` events has its positives and its negatives (negs [hi - lo, K]) scored against
+    the bank as it stood before the batch, and is inserted.  window=None is EdgeBank-inf (score 1 for a pair the bank
+    holds); with a window (a duration, edgebank_window) a pair scores 1 iff t_last >= t_hi - window, t_hi the largest
+    float32 stamp inserted so far, the difference taken in float32 (EdgeBank-tw; before anything is inserted nothing
+    scores).  loader: a SplitLoader or anything with .src / .dst / .t (stamps are taken as float32, the event table's
+    type).  Ranks are tie-averaged and the result is the mean over batches of the batch MRR, as
+    tgnx.tgb_negs.edgebank_mrr reports it; window=None equals it exactly on the same negatives.  Host reads: the
+    PairSet's growth schedule and one at the end."""
+    import numpy as np
+
+    from .pairset import PairSet, min_capacity
+    d = getattr(loader, "data", loader)
+    lo, hi, batch = int(lo), int(hi), int(batch)
+    dev = torch.device(device)
+    src, dst = torch.as_tensor(d.src).to(dev, torch.long), torch.as_tensor(d.dst).to(dev, torch.long)
+    t_host = torch.as_tensor(d.t).to(torch.float32).cpu()
+    t = t_host.to(dev)
+    E = int(src.numel())
+    negs = torch.as_tensor(negs).to(dev, torch.long)
+    if not (0 <= lo <= hi <= E) or batch <= 0 or negs.dim() != 2 or negs.shape[0] != hi - lo:
+        raise ValueError(f"edgebank_stream: rows [{lo}, {hi}) batch {batch} outside the {E}-event stream, or negs is "
+                         f"not [hi - lo, K]")
+    if window is not None and not float(window) >= 0.0:
+        raise ValueError("edgebank_stream: window must be a duration >= 0")
+    n, K = hi - lo, int(negs.shape[1])
+    if n == 0:
+        return float("nan")
+    num_nodes = int(max(int(src.max()), int(dst.max()), int(negs.max()) if negs.numel() else 0)) + 1
+    bank = PairSet(num_nodes, min_capacity(batch), device=dev)
+    bank.insert(src[:lo], dst[:lo], t[:lo])
+    t_np = t_host.numpy()
+    t_hi = np.float32(t_np[:lo].max()) if lo else None
+    rrs = []
+    for a in range(lo, hi, batch):
+        b = min(batch, hi - a)
+        s, p, ng = src[a:a + b], dst[a:a + b], negs[a - lo:a - lo + b]
+        if window is None:
+            since = None
+        elif t_hi is None:
+            since = float("inf")
+        else:
+            since = float(np.float32(t_hi - np.float32(window)))
+        pos = bank.contains(s, p, since).double()
+        neg = bank.contains(s.repeat_interleave(K), ng.reshape(-1), since).view(b, K).double()
+        rank = 0.5 * ((neg > pos[:, None]).sum(1) + (neg >= pos[:, None]).sum(1)).double() + 1.0
+        rrs.append(1.0 / rank)
+        bank.insert(s, p, t[a:a + b])
+        m = np.float32(t_np[a:a + b].max())
+        t_hi = m if t_hi is None else max(t_hi, m)
+    rr = torch.cat(rrs).cpu().numpy()
+    return float(np.mean([rr[a:a + batch].mean() for a in range(0, n, batch)]))
+
+
+@torch.no_grad()
+def enable_pair_history(model, neighbor_loader, capacity=None):
+    """Turn on the live pair history of the engine train() / test() attached to the model
+    (TgnEngine.enable_pair_history): observe() and the per-batch test path record their batches from here on; rows
+    trained or validated by the resident passes are recorded with the engine's record_pairs(lo, hi)."""
+    _bound_engine(model, neighbor_loader, "enable_pair_history").enable_pair_history(capacity)
+
+
+@torch.no_grad()
+def seen(model, neighbor_loader, src, dst, since=None):
+    """bool[n] on the device: has src[i] ever interacted with dst[i] in the recorded stream (TgnEngine.seen)."""
+    return _bound_engine(model, neighbor_loader, "seen").seen(src, dst, since)
+
+
 @torch.no_grad()
 def save_stream(model, neighbor_loader, f):
     """torch.save the engine's stream state (TgnEngine.stream_state; no parameters: the model's state_dict() has them)
     to the path or file object f.  Straight after train() the memory is switched to eval first, as test(), recommend()
-    and observe() do, so the file holds a serving state.  Small when taken after compact()."""
+    and observe() do, so the file holds a serving state.  Small when taken after compact().  With the pair history
+    enabled the file also carries it under "pair_history" (TgnEngine.pair_history_state, moved to the host);
+    stream_state()'s own keys and format are unchanged, and TgnEngine.load_stream_state reads its own keys only, so it
+    takes such a file as it is (ignoring the history: load_stream carries it)."""
     eng = _bound_engine(model, neighbor_loader, "save_stream")
     if eng._mode_train:
         eng.flush()
         eng._mode_train = False
-    torch.save(eng.stream_state(), f)
+    state = eng.stream_state()
+    if eng._pairs is not None:
+        ph = eng.pair_history_state()
+        state["pair_history"] = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in ph.items()}
+    torch.save(state, f)
 
 
 @torch.no_grad()
 def load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
     """Load a save_stream file into the engine attached to the model — or, in a fresh process where none is, into a
     new engine over a one-row table (optimizer and dst_nodes as train() would have given it) — and leave it in eval
-    mode: observe(), recommend() and test() go on from the saved state (TgnEngine.load_stream_state)."""
+    mode: observe(), recommend() and test() go on from the saved state (TgnEngine.load_stream_state).  A file that
+    carries a pair history enables it and loads it; a file without one leaves an enabled history empty."""
     m = _owner(model)
     eng = getattr(m, "_tgnx_engine", None)
     state = torch.load(f, map_location="cpu")
@@ -455,7 +568,12 @@ def load_stream(model, neighbor_loader, f, optimizer=None, dst_nodes=None):
         eng.keep_grads = False
         eng._bound = None
         m._tgnx_engine = eng
+    ph = state.pop("pair_history", None)
     eng.load_stream_state(state)
+    if ph is not None:
+        eng.load_pair_history_state(ph)
+    elif eng._pairs is not None:
+        eng.clear_pair_history()
     eng._mode_train = False
     neighbor_loader.cur_e_id = eng.num_events
     return eng.num_events
