@@ -1020,7 +1020,10 @@ int tgnx_embed_knn(int64_t n_q, int64_t n_cand, int64_t D, const float* z_q, con
  * + 1e-16 in the denominator), out_i = Σ_p α_p (v_p + e_p) (the root weight / skip is the caller's Linear).
  * e may be NULL (no edge features).  alpha [E, H] is written.  1 <= heads <= 8, heads * C <= 256.  indptr is
  * clamped to [0, n_edges].  No attention dropout (eval, or dropout 0).
- * Backward: dq [n_dst, H*C], dk / dv / de [E, H*C] (de = dk + dv, needed only with e) from dout and alpha. */
+ * Backward: dq [n_dst, H*C], dk / dv / de [E, H*C] (de = dk + dv, needed only with e) from dout and alpha.
+ * indptr need not span all n_edges rows.  An edge row that no destination owns (a row before indptr[0] or from
+ * indptr[n_dst] on, indptr non-decreasing; every row when n_dst == 0) takes part in nothing: both calls write
+ * every row of their per-edge outputs, and such a row gets alpha = 0 and dk = dv = de = 0. */
 int tgnx_edge_attn_fwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* q,
                        const float* k, const float* v, const float* e, const int64_t* indptr, float* out,
                        float* alpha, void* stream);

@@ -10,12 +10,14 @@ functions of tgnx/ops.py) against torch CPU autograd of the matching oracle / to
   aggregate_last / _mean       gradient through oracle last_aggregate (BIT-EXACT: a scatter) / mean_aggregate (1e-4)
   linear                       torch.nn.Linear, 2e-5 / 1e-4
 
-Errors are max |a - b| relative to max(|b|, 1) of the reference tensor (test_gpu_module_ops._close); the
+Errors are max |a - b| relative to max(|b|, 1) of the reference tensor (module_ref.close); the
 tolerances cover reassociation only (MFMA GEMM / fixed-order column sums vs torch's CPU order).  Every backward
 op is bit-identical when run twice; a non-contiguous or host tensor raises RuntimeError."""
 import numpy as np
 import pytest
 import torch
+
+from module_ref import close as _close
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -25,15 +27,6 @@ FWD_TOL, GRAD_TOL = 2e-5, 1e-4
 def _ops():
     from tgnx import ops
     return ops.load()
-
-
-def _close(a, b, tol, what=""):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    scale = max(float(b.abs().max()), 1.0) if b.numel() else 1.0
-    err = float((a - b).abs().max()) if b.numel() else 0.0
-    print(f"{what}: err {err:.3e} scale {scale:.3e} rel {err / scale:.3e} tol {tol:g}")
-    assert err <= tol * scale, (what, err, scale)
 
 
 def _dev(x, grad=False):

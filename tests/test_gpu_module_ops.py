@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from module_ref import close as _close
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 
@@ -63,13 +65,6 @@ def test_msg_agg_rejects_out_of_range_index():
         ns.msg_agg_last(msg, index, t, 3)
     with pytest.raises(RuntimeError, match="outside"):
         ns.msg_agg_mean(msg, index - 1, 3)
-
-
-def _close(a, b, tol):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    scale = max(float(b.abs().max()), 1.0) if b.numel() else 1.0
-    err = float((a - b).abs().max()) if b.numel() else 0.0
-    assert err <= tol * scale, (err, scale)
 
 
 @pytest.mark.parametrize("cell", ["gru", "rnn"])

@@ -393,6 +393,47 @@ __global__ void __launch_bounds__(OPS_BLOCK) attn_bwd(int64_t n_dst, int64_t E, 
     if (row.ok[r]) dq[i * HC + lane + 64 * r] = dq_acc[r];
 }
 
+// The kernels above write the edge rows [indptr[0], indptr[n_dst]) (clamped as edge_range clamps) and nothing else.
+// This launch, ahead of them on the stream, zeroes the rows before and after that span (every row when n_dst == 0)
+// of up to four per-edge outputs of `width` floats, so that a row no destination owns reads 0.  With a
+// non-decreasing indptr the two launches write disjoint rows; with any other the attention kernel, being later,
+// wins.  A grid-stride loop over the elements outside the span: the grid is sized for all E rows, and a block with
+// nothing to do leaves after reading the two ends of indptr.
+struct AttnRows {
+  float* p[4];
+  int width[4];
+};
+
+__global__ void __launch_bounds__(OPS_BLOCK) attn_zero_unowned(int64_t n_dst, int64_t E, const int64_t* indptr,
+                                                               AttnRows o) {
+  int64_t lo = 0, hi = 0;
+  if (n_dst > 0) {
+    lo = min(max(indptr[0], (int64_t)0), E);
+    hi = min(max(indptr[n_dst], lo), E);
+  }
+  const int64_t rows = lo + (E - hi);  // rows [0, lo) and [hi, E)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (!o.p[j]) continue;
+    const int64_t w = o.width[j], total = rows * w;
+    for (int64_t x = blockIdx.x * (int64_t)OPS_BLOCK + threadIdx.x; x < total; x += (int64_t)gridDim.x * OPS_BLOCK) {
+      const int64_t r = x / w;
+      o.p[j][(r < lo ? r : r - lo + hi) * w + x % w] = 0.f;
+    }
+  }
+}
+
+int attn_zero_launch(int64_t n_dst, int64_t E, const int64_t* indptr, const AttnRows& o, hipStream_t s) {
+  int wmax = 0;
+  for (int j = 0; j < 4; ++j)
+    if (o.p[j]) wmax = std::max(wmax, o.width[j]);
+  if (E == 0 || wmax == 0) return TGNX_OK;
+  const int64_t blocks = std::min<int64_t>(ceil_div(E * wmax, OPS_BLOCK), 1024);
+  hipLaunchKernelGGL(attn_zero_unowned, dim3((unsigned)blocks), dim3(OPS_BLOCK), 0, s, n_dst, E, indptr, o);
+  TGNX_LAUNCH_CHECK("attn_zero_unowned");
+  return TGNX_OK;
+}
+
 template <template <int> class K, typename... A>
 int attn_dispatch(int HC, int64_t n_dst, hipStream_t s, A... args) {
   const dim3 grid((unsigned)ceil_div(n_dst, WAVES));
@@ -529,10 +570,14 @@ int tgnx_edge_attn_fwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t ch
   TGNX_CHECK_ARG(n_dst >= 0 && n_edges >= 0 && heads > 0 && heads <= HMAX && channels > 0,
                  "tgnx_edge_attn_fwd: bad sizes (1 <= heads <= %d)", HMAX);
   TGNX_CHECK_ARG((int64_t)heads * channels <= 256, "tgnx_edge_attn_fwd: heads * channels must be <= 256");
-  if (n_dst == 0) return TGNX_OK;
-  TGNX_CHECK_ARG(q && indptr && out && (n_edges == 0 || (k && v && alpha)), "tgnx_edge_attn_fwd: null pointer");
-  const int rc = attn_dispatch<FwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
-                                     (int)channels, q, k, v, e, indptr, out, alpha);
+  TGNX_CHECK_ARG(n_dst == 0 || (q && indptr && out && (n_edges == 0 || (k && v && alpha))),
+                 "tgnx_edge_attn_fwd: null pointer");
+  // rows of alpha that no destination owns (all of them without destinations) are zero, not left as they were
+  int rc = attn_zero_launch(n_dst, n_edges, indptr, AttnRows{{alpha, nullptr, nullptr, nullptr}, {heads, 0, 0, 0}},
+                            as_stream(stream));
+  if (rc != TGNX_OK || n_dst == 0) return rc;
+  rc = attn_dispatch<FwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
+                           (int)channels, q, k, v, e, indptr, out, alpha);
   if (rc != TGNX_OK) return rc;
   TGNX_LAUNCH_CHECK("attn_fwd");
   return TGNX_OK;
@@ -544,11 +589,16 @@ int tgnx_edge_attn_bwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t ch
   TGNX_CHECK_ARG(n_dst >= 0 && n_edges >= 0 && heads > 0 && heads <= HMAX && channels > 0,
                  "tgnx_edge_attn_bwd: bad sizes (1 <= heads <= %d)", HMAX);
   TGNX_CHECK_ARG((int64_t)heads * channels <= 256, "tgnx_edge_attn_bwd: heads * channels must be <= 256");
-  if (n_dst == 0) return TGNX_OK;
-  TGNX_CHECK_ARG(dout && q && indptr && dq && (n_edges == 0 || (k && v && alpha && dk && dv)) && (!e || de || !n_edges),
+  TGNX_CHECK_ARG(n_dst == 0 || (dout && q && indptr && dq && (n_edges == 0 || (k && v && alpha && dk && dv)) &&
+                                (!e || de || !n_edges)),
                  "tgnx_edge_attn_bwd: null pointer");
-  const int rc = attn_dispatch<BwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
-                                     (int)channels, dout, q, k, v, e, indptr, alpha, dq, dk, dv, de);
+  // as the forward: dk / dv / de rows that no destination owns are zero
+  const int HC = heads * channels;
+  int rc = attn_zero_launch(n_dst, n_edges, indptr, AttnRows{{dk, dv, de, nullptr}, {HC, HC, HC, 0}},
+                            as_stream(stream));
+  if (rc != TGNX_OK || n_dst == 0) return rc;
+  rc = attn_dispatch<BwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
+                           (int)channels, dout, q, k, v, e, indptr, alpha, dq, dk, dv, de);
   if (rc != TGNX_OK) return rc;
   TGNX_LAUNCH_CHECK("attn_bwd");
   return TGNX_OK;

@@ -75,7 +75,10 @@ class _EdgeAttention(torch.autograd.Function):
 def edge_attention(q, k, v, e, indptr, heads):
     """TransformerConv's attention (PyG semantics, emb_module.py:21-29) with autograd: q [n_dst, H*C] per
     destination; k, v, e [E, H*C] per edge, destination i's edges the rows [indptr[i], indptr[i+1]) (e may be
-    None).  Returns (out [n_dst, H*C], alpha [E, H]); gradients flow to q, k, v, e."""
+    None).  Returns (out [n_dst, H*C], alpha [E, H]); gradients flow to q, k, v, e.  1 <= heads <= 8 and
+    H*C <= 256 (RuntimeError otherwise).  indptr (non-decreasing) need not span all E rows: an edge row that no
+    destination owns, before indptr[0] or from indptr[-1] on, and every row when n_dst == 0, has alpha = 0 and
+    receives zero gradients in k, v and e."""
     return _EdgeAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(),
                                 None if e is None else e.contiguous(), indptr, int(heads))
 
