@@ -103,6 +103,8 @@ int tgnx_block_ids_host(const int64_t* src, const int64_t* dst, int64_t num_even
 #define TGNX_K_KV 10             /* TGN: kv_reduce ‖ dW_edge ‖ dEnc·W_e launch */
 #define TGNX_K_PROJ 11           /* TGN: q / k / v / skip projections launch */
 #define TGNX_K_WGRAD3 12         /* TGN: dW_gru ‖ dX_enc ‖ message stores ‖ descriptor snapshot launch */
+#define TGNX_K_EXPLAIN 13        /* TGN: tgn_explain_rows (tgnx_tgn_explain's last launch) */
+#define TGNX_K_LOO_ROWS 14       /* loo_rows (tgnx_link_predictor_loo's row kernel, after its four GEMMs) */
 int tgnx_probe_enable(int32_t kernel_id);
 int tgnx_probe_read(double* total_ms, int64_t* launches);
 /* Workgroup timeline stamps (diagnostic; measurement only): a library built with -DTGNX_STAMPS records, for
@@ -682,6 +684,36 @@ int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg);
 int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
                    float* out_z /* [n, mem_dim] */, int64_t* n_invalid /* device, caller-zeroed, may be NULL */,
                    void* stream);
+/* Why a link score is what it is: tgnx_tgn_embed for the listed nodes with, per node, the ring slots
+ * its embedding attended over, the attention weights, and the embedding recomputed with a slot (or a neighbour) absent.
+ * The launches are tgnx_tgn_embed's with tgn_explain_rows in tgn_embed_gather's place: the same claim / mark /
+ * inference forward, the same private ctl copy and ERR OR-back, the same capacity (n <= tgnx_tgn_embed_max_nodes), the
+ * same read-only guarantees (GEN advances by one; ERR may take the overflow bit, and every output is then as for an
+ * invalid id), ids outside [0, num_nodes) counted into *n_invalid and never used as an index.  K = cfg->ring,
+ * D = cfg->mem_dim.  Per listed node i, whose root level samples the ne valid slots of its ring row in slot order:
+ *   z[i, D]            the embedding, bit for bit tgnx_tgn_embed's row;
+ *   count[i]           ne;
+ *   slot_eid[i, K], slot_nbr[i, K]   the slot's event row and the neighbour's node id, -1 past ne;
+ *   alpha[i, K, 2]     the root level's eval attention per head (a = q · (k + e) / sqrt(C), max subtracted, + 1e-16 in
+ *                      the denominator), 0 past ne;
+ *   loo_z[i, K, D]     row j: the embedding with the slots S_j absent — S_j = {j} (TGNX_EXPLAIN_SLOT) or every slot
+ *                      u with slot_nbr[u] == slot_nbr[j] (TGNX_EXPLAIN_NEIGHBOUR) — recomputed from the scores (max,
+ *                      exponentials and denominator over the remaining slots, summed in slot order, + the skip row),
+ *                      not derived from z by division; an empty remainder gives the skip row, the embedding of a node
+ *                      without edges.  Rows j >= ne are zero.
+ * An invalid id: zero rows, count 0, slots -1.  loo_z may be NULL (the attention alone).  At layers = 2 alpha is the
+ * root level's (conv2 over the node's own ring row) and loo_z must be NULL: removing an edge there also changes the
+ * node's own hop-1 row, hence the second hop's query and skip; a non-NULL loo_z is TGNX_EINVAL before any launch.
+ * No atomics in tgn_explain_rows, every loop bounded by the ring width; a row does not depend on the grid or on how a
+ * node list is chunked.  No host synchronisation, no allocation.
+ * Test: tests/test_gpu_tgn_explain.py (against the oracle with the ring slots masked out of its sampler). */
+#define TGNX_EXPLAIN_SLOT 0
+#define TGNX_EXPLAIN_NEIGHBOUR 1
+int tgnx_tgn_explain(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                     int32_t mode, float* z /* [n, D] */, int32_t* count /* [n] */, int64_t* slot_eid /* [n, K] */,
+                     int64_t* slot_nbr /* [n, K] */, float* alpha /* [n, K, 2] */,
+                     float* loo_z /* [n, K, D], may be NULL */, int64_t* n_invalid /* device, may be NULL */,
+                     void* stream);
 /* Score-free ingestion: the state update of tgnx_tgn_eval_step for the batch ctl describes (as after
  * tgnx_tgnn_advance(..., train = 0)), without negatives and without the forward that scores them — update_state in
  * eval order (memory_module.py:126-138 with training == False: store the batch's messages, aggregate and run the
@@ -892,6 +924,26 @@ int tgnx_link_predictor(int64_t n_src, int64_t M, int64_t d_in, int64_t D, const
                         const float* w_src, const float* b_src, const float* w_dst, const float* b_dst,
                         const float* w_out, const float* b_out, int32_t sigmoid, float* out, void* ws,
                         size_t ws_bytes, void* stream);
+
+/* Leave-one-out link logits (csrc/tgnx_explain.hip).  z [n, d_in] and loo_z [n, K, d_in] hold the
+ * embedding and the K leave-one-out embeddings of each of n UNIQUE nodes (tgnx_tgn_explain's z and loo_z), count [n]
+ * how many of a node's K rows exist; pair p names rows s = src_row[p] and d = dst_row[p].  With logit(a, b) =
+ * w_out · relu(W_src a + b_src + W_dst b + b_dst) + b_out (weights as tgnx_link_predictor; b_src / b_dst may be NULL):
+ *   base[p] = logit(z[s], z[d]);  src_logit[p, j] = logit(loo_z[s, j], z[d]);  dst_logit[p, j] = logit(z[s], loo_z[d, j])
+ * — each side varied alone, also when s == d — and an entry with j >= count of the varied node holds base[p]'s bits.
+ * Every unique row is projected once on tgnx_gemm_f32 (4 GEMMs, O(n K D^2) whatever P), then one row kernel runs the
+ * 1 + 2 K relu-dot chains of each pair, each a sequential fma chain over the D columns in ascending order: a logit's
+ * bits depend on its two rows, not on the grid or the order of the pairs.  A row index outside [0, n) is never
+ * dereferenced: the pair's outputs are NaN and *status (device int64, caller-zeroed) becomes 1.  1 <= K <= 64,
+ * D <= 256, n, P < 2^24; P = 0 does nothing.  No atomics, no allocation, no host synchronisation.
+ * ws: tgnx_link_predictor_loo_ws_bytes bytes.  Test: tests/test_gpu_link_loo.py (float64). */
+size_t tgnx_link_predictor_loo_ws_bytes(int64_t n, int64_t K, int64_t P, int64_t d_in, int64_t D);
+int tgnx_link_predictor_loo(int64_t n, int64_t K, int64_t P, int64_t d_in, int64_t D, const float* z,
+                            const float* loo_z, const int32_t* count, const int64_t* src_row, const int64_t* dst_row,
+                            const float* w_src, const float* b_src, const float* w_dst, const float* b_dst,
+                            const float* w_out, const float* b_out, float* base /* [P] */,
+                            float* src_logit /* [P, K] */, float* dst_logit /* [P, K] */, int64_t* status, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* LinkPredictor over ALL pairs with the selection fused in (csrc/tgnx_topk.hip): for every source row q the k
  * candidates with the largest logit[q][c] = w_out · relu(W_src z_src[q] + b_src + W_dst z_cand[c] + b_dst) + b_out,

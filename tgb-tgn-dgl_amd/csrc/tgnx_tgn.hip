@@ -4744,6 +4744,107 @@ __global__ void __launch_bounds__(256) tgn_embed_gather(Ctx c, int64_t* live_ctl
   }
 }
 
+// tgnx_tgn_explain's last launch, in tgn_embed_gather's place (c: the root level's view, c.ctl the private copy): a
+// wave per listed node i, with the root level's P / Ep / e_j / ceoff / Zc rows the forward left.  It writes
+//   z[i]              the Zc row (tgn_embed_gather's copy);
+//   count[i]          ne, the node's sampled edges;
+//   slot_eid / nbr    the ring row's valid slots in slot order (the order of the level's edges: tgn_agg_emit places
+//                     slot j at ceoff + the valid slots before j), -1 past ne;
+//   alpha[i][j][h]    the eval attention of edge j — attn_centre's expression restated (a = q · (k + e) / sqrt(C) by
+//                     the same wave sum, max subtracted, + 1e-16); that kernel is left as measured;
+//   loo_z[i][j]       (loo_z != nullptr) the embedding with the slots S_j absent, recomputed: the max, the
+//                     exponentials, the denominator and the slot-ordered sum over u not in S_j, + the skip row.
+//                     S_j = {j} (mode 0) or every slot naming slot j's neighbour (mode 1).  An empty remainder leaves
+//                     the skip row.  Rows j >= ne are zero.
+// The v + e rows sit in LDS (a wave's K rows; every lane reads back only what it wrote: no barrier), the scores one
+// per lane (K <= KMAX < 64).  Every loop is bounded by ne <= K; no atomics; a row's values depend on neither the grid
+// nor the other nodes of the list.  An id outside [0, N), or a nonzero ERR: zeros, count 0, slots -1.
+__global__ void __launch_bounds__(256) tgn_explain_rows(Ctx c, int64_t* live_ctl, const int64_t* nodes, int n, int mode,
+                                                        float* out_z, int* out_count, int64_t* out_eid,
+                                                        int64_t* out_nbr, float* out_alpha, float* out_loo) {
+  extern __shared__ float ex_lds[];
+  const int64_t err = c.ctl[TGNX_CTL_ERR];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && err != live_ctl[TGNX_CTL_ERR]) live_ctl[TGNX_CTL_ERR] |= err;
+  const int lane = threadIdx.x & 63, D = c.D, K = c.K, C = c.C, HC = c.HC;
+  float* sv = ex_lds + (size_t)(threadIdx.x >> 6) * K * HC;   // this wave's [K][HC] v + e rows
+  const float on = f01(lane < C);
+  const int l0 = min(lane, C - 1);
+  const float sqc = sqrtf((float)C);
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const int64_t v = nodes[i];
+    const bool ok = err == 0 && v >= 0 && v < c.N;
+    const int x = ok ? root_row(c, v) : 0;
+    const int e0 = ok ? c.ceoff[x] : 0;
+    const int ne = ok ? min(max(c.ceoff[x + 1] - e0, 0), K) : 0;
+    const float* zr = c.Zc + (int64_t)x * HC;
+    for (int k = lane; k < D; k += WAVE) out_z[(int64_t)i * D + k] = ok ? zr[k] : 0.f;
+    if (lane == 0) out_count[i] = ne;
+    // the ring row's valid slots, compacted: lane j gets the j-th of them
+    const int ls = min(lane, K - 1);
+    const int64_t e_l = ok ? c.eid[v * K + ls] : -1, u_l = ok ? c.nbr[v * K + ls] : -1;
+    const uint64_t valid = __ballot(ok && lane < K && e_l >= 0);
+    int64_t my_e = -1, my_u = -1;
+    for (int j = 0; j < K; ++j) {
+      const int64_t ej = shfl_i64(e_l, j), uj = shfl_i64(u_l, j);
+      const int pos = __popcll(valid & ((1ull << j) - 1ull));
+      if (((valid >> j) & 1ull) && lane == pos && pos < ne) { my_e = ej; my_u = uj; }
+    }
+    if (lane < K) {
+      out_eid[(int64_t)i * K + lane] = my_e;
+      out_nbr[(int64_t)i * K + lane] = my_u;
+    }
+    // scores, one per lane, and the v + e rows
+    float my0 = -INFINITY, my1 = -INFINITY, sk0 = 0.f, sk1 = 0.f;
+    if (ne > 0) {
+      const float* Pi = c.P + (int64_t)c.cent_loc[x] * 4 * HC;
+      const float q0 = Pi[l0], q1 = Pi[C + l0];
+      sk0 = Pi[3 * HC + l0];
+      sk1 = Pi[3 * HC + C + l0];
+      const int jl = c.e_j[e0 + min(lane, ne - 1)];
+      for (int e = 0; e < ne; ++e) {
+        const float* Pj = c.P + (int64_t)lane_i(jl, e) * 4 * HC;
+        const float* Ee = c.Ep + (int64_t)(e0 + e) * HC;
+        const float ea = Ee[l0], eb = Ee[C + l0];
+        const float p0 = wave_sum_f(q0 * (Pj[HC + l0] + ea) * on), p1 = wave_sum_f(q1 * (Pj[HC + C + l0] + eb) * on);
+        if (lane == e) { my0 = p0; my1 = p1; }
+        if (lane < C) {
+          sv[e * HC + lane] = Pj[2 * HC + l0] + ea;
+          sv[e * HC + C + lane] = Pj[2 * HC + C + l0] + eb;
+        }
+      }
+      if (lane < ne) { my0 /= sqc; my1 /= sqc; }
+    }
+    {
+      const float mx0 = wave_max_f(my0), mx1 = wave_max_f(my1);
+      const float ex0 = lane < ne ? expf(my0 - mx0) : 0.f, ex1 = lane < ne ? expf(my1 - mx1) : 0.f;
+      const float a0 = ex0 / (wave_sum_f(ex0) + 1e-16f), a1 = ex1 / (wave_sum_f(ex1) + 1e-16f);
+      if (lane < K) {
+        out_alpha[((int64_t)i * K + lane) * 2] = a0;
+        out_alpha[((int64_t)i * K + lane) * 2 + 1] = a1;
+      }
+    }
+    if (!out_loo) continue;  // (uniform)
+    float* lz = out_loo + (int64_t)i * K * D;
+    for (int j = 0; j < ne; ++j) {
+      const bool gone = mode == 1 ? my_u == shfl_i64(my_u, j) : lane == j;
+      const bool keep = lane < ne && !gone;
+      const float mx0 = wave_max_f(keep ? my0 : -INFINITY), mx1 = wave_max_f(keep ? my1 : -INFINITY);
+      const float ex0 = keep ? expf(my0 - mx0) : 0.f, ex1 = keep ? expf(my1 - mx1) : 0.f;
+      const float a0 = ex0 / (wave_sum_f(ex0) + 1e-16f), a1 = ex1 / (wave_sum_f(ex1) + 1e-16f);
+      float o0 = 0.f, o1 = 0.f;
+      for (int u = 0; u < ne; ++u) {  // (a of an absent slot is 0: it adds an exact zero)
+        o0 += sv[u * HC + l0] * lane_f(a0, u);
+        o1 += sv[u * HC + C + l0] * lane_f(a1, u);
+      }
+      if (lane < C) {
+        lz[(int64_t)j * D + lane] = o0 + sk0;
+        lz[(int64_t)j * D + C + lane] = o1 + sk1;
+      }
+    }
+    for (int k = ne * D + lane; k < K * D; k += WAVE) lz[k] = 0.f;
+  }
+}
+
 static size_t carve(size_t& off, size_t bytes) {
   size_t o = off;
   off += (bytes + 255) & ~size_t(255);
@@ -6256,6 +6357,24 @@ int64_t tgnx_tgn_embed_max_nodes(const tgnx_tgn_config* cfg) {
   if (check_cfg(cfg)) return 0;
   return make_caps(cfg).R1cap;
 }
+// The launches every node-list query shares (tgnx_tgn_embed, tgnx_tgn_embed_into, tgnx_tgn_explain): claim, mark and the
+// inference forward of the listed roots, on the private copy of the control block (see tgn_embed_claim).  cr: the
+// root-level view the query's own last launch reads; live: the engine's control block (that launch ORs ERR into it)
+static int node_list_forward(hipStream_t s, Ctx c, const Caps& k, const WsLay& W, void* wsp, const int64_t* nodes,
+                             int nn, int64_t* n_invalid, Ctx& cr, int64_t*& live) {
+  char* ws = reinterpret_cast<char*>(wsp);
+  int* own = reinterpret_cast<int*>(ws + W.own);
+  live = c.ctl;
+  c.ctl = reinterpret_cast<int64_t*>(ws + W.qctl);
+  c.errw = c.ctl + TGNX_CTL_ERR;
+  const int nslot = gridn(nn, 256, 4096);
+  tgn_embed_claim<<<nslot, 256, 0, s>>>(c, live, own, nodes, nn, n_invalid);
+  TGNX_LAUNCH_CHECK("tgn_embed_claim");
+  tgn_embed_mark<<<nslot, 256, 0, s>>>(c, own, nodes, nn);
+  TGNX_LAUNCH_CHECK("tgn_embed_mark");
+  // role 0 alone: roles >= 1 build the insert / store plans of a batch's events, and there is no batch
+  return infer_forward(s, c, k, k.R1cap, 1, cr);
+}
 // into: out_z is a table indexed by node id (tgnx_tgn_embed_into); else row i is nodes[i]'s
 static int embed_impl(const char* who, const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes,
                       int64_t n, float* out_z, int64_t* n_invalid, bool into, void* stream) {
@@ -6271,20 +6390,10 @@ static int embed_impl(const char* who, const tgnx_tgn_config* cfg, const tgnx_tg
   if (n == 0) return TGNX_OK;
   TGNX_CHECK_ARG(nodes && out_z, "%s: null pointer", who);
   hipStream_t s = as_stream(stream);
-  char* ws = reinterpret_cast<char*>(buf->ws);
-  int* own = reinterpret_cast<int*>(ws + W.own);
-  int64_t* live = c.ctl;
-  c.ctl = reinterpret_cast<int64_t*>(ws + W.qctl);
-  c.errw = c.ctl + TGNX_CTL_ERR;
   const int nn = (int)n;
-  const int nslot = gridn(n, 256, 4096);
-  tgn_embed_claim<<<nslot, 256, 0, s>>>(c, live, own, nodes, nn, n_invalid);
-  TGNX_LAUNCH_CHECK("tgn_embed_claim");
-  tgn_embed_mark<<<nslot, 256, 0, s>>>(c, own, nodes, nn);
-  TGNX_LAUNCH_CHECK("tgn_embed_mark");
-  // role 0 alone: roles >= 1 build the insert / store plans of a batch's events, and there is no batch
   Ctx cr;
-  if ((rc = infer_forward(s, c, k, k.R1cap, 1, cr))) return rc;
+  int64_t* live;
+  if ((rc = node_list_forward(s, c, k, W, buf->ws, nodes, nn, n_invalid, cr, live))) return rc;
   if (into)
     tgn_embed_gather<true><<<gridn(n, 4, 2048), 256, 0, s>>>(cr, live, nodes, nn, out_z);
   else
@@ -6299,6 +6408,41 @@ int tgnx_tgn_embed(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, cons
 int tgnx_tgn_embed_into(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
                         float* table, void* stream) {
   return embed_impl("tgnx_tgn_embed_into", cfg, buf, nodes, n, table, nullptr, true, stream);
+}
+
+// node_list_forward with tgn_explain_rows as the last launch: the listed nodes' embeddings, their
+// sampled slots, the root level's attention and (1 hop) the leave-one-out embeddings
+int tgnx_tgn_explain(const tgnx_tgn_config* cfg, const tgnx_tgn_buffers* buf, const int64_t* nodes, int64_t n,
+                     int32_t mode, float* z, int32_t* count, int64_t* slot_eid, int64_t* slot_nbr, float* alpha,
+                     float* loo_z, int64_t* n_invalid, void* stream) {
+  const char* who = "tgnx_tgn_explain";
+  Ctx c;
+  Caps k;
+  WsLay W;
+  TGNX_CHECK_ARG(cfg && buf, "%s: null config or buffers", who);
+  TGNX_CHECK_ARG(mode == TGNX_EXPLAIN_SLOT || mode == TGNX_EXPLAIN_NEIGHBOUR,
+                 "%s: mode must be TGNX_EXPLAIN_SLOT (0) or TGNX_EXPLAIN_NEIGHBOUR (1), got %d", who, mode);
+  int rc = make_ctx(cfg, buf, cfg->max_neg < 1 ? 1 : cfg->max_neg, c, k, W);
+  if (rc) return rc;
+  TGNX_CHECK_ARG(!loo_z || k.layers == 1,
+                 "%s: leave-one-out embeddings are built for the 1-hop embedding (layers = 1); pass loo_z = NULL for "
+                 "the attention alone", who);
+  TGNX_CHECK_ARG(n >= 0 && n <= k.R1cap, "%s: n = %lld beyond tgnx_tgn_embed_max_nodes = %d", who, (long long)n,
+                 k.R1cap);
+  if (n == 0) return TGNX_OK;
+  TGNX_CHECK_ARG(nodes && z && count && slot_eid && slot_nbr && alpha, "%s: null pointer", who);
+  hipStream_t s = as_stream(stream);
+  const int nn = (int)n;
+  Ctx cr;
+  int64_t* live;
+  if ((rc = node_list_forward(s, c, k, W, buf->ws, nodes, nn, n_invalid, cr, live))) return rc;
+  const size_t smem = (size_t)4 * c.K * c.HC * sizeof(float);  // <= 4 * KMAX * TDMAX * 4 = 64 KB
+  probe_begin(TGNX_K_EXPLAIN, s);
+  launch_k(tgn_explain_rows, dim3(gridn(n, 4, 2048)), dim3(256), (uint32_t)smem, s, cr, live, nodes, nn, (int)mode, z,
+           count, slot_eid, slot_nbr, alpha, loo_z);
+  probe_end(TGNX_K_EXPLAIN, s);
+  TGNX_LAUNCH_CHECK("tgn_explain_rows");
+  return TGNX_OK;
 }
 
 // eval_step_impl's state update without its forward: see tgn_observe_mark

@@ -705,6 +705,48 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_rank(
   return {gt, eq, n, tl};
 }
 
+// leave-one-out link logits (tgnx_link_predictor_loo, csrc/tgnx_explain.hip):
+// (base [P], src_logit [P, K], dst_logit [P, K], status [1] int64: 1 when a row index lay outside [0, n))
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> predictor_loo(
+    const at::Tensor& z, const at::Tensor& loo_z, const at::Tensor& count, const at::Tensor& src_row,
+    const at::Tensor& dst_row, const at::Tensor& w_src, const c10::optional<at::Tensor>& b_src, const at::Tensor& w_dst,
+    const c10::optional<at::Tensor>& b_dst, const at::Tensor& w_out, const at::Tensor& b_out) {
+  dev_tensor(z, at::kFloat, "z");
+  dev_tensor(loo_z, at::kFloat, "loo_z");
+  dev_tensor(count, at::kInt, "count");
+  dev_tensor(src_row, at::kLong, "src_row");
+  dev_tensor(dst_row, at::kLong, "dst_row");
+  dev_tensor(w_src, at::kFloat, "w_src");
+  dev_tensor(w_dst, at::kFloat, "w_dst");
+  dev_tensor(w_out, at::kFloat, "w_out");
+  dev_tensor(b_out, at::kFloat, "b_out");
+  TORCH_CHECK(z.dim() == 2 && loo_z.dim() == 3 && loo_z.size(0) == z.size(0) && loo_z.size(2) == z.size(1),
+              "z [n, d] and loo_z [n, K, d]");
+  const int64_t n = z.size(0), K = loo_z.size(1), d_in = z.size(1), D = w_src.size(0), P = src_row.numel();
+  TORCH_CHECK(K >= 1 && K <= 64, "loo_z must have 1 <= K <= 64 rows per node, got ", K);
+  TORCH_CHECK(count.numel() == n, "count must have n entries");
+  TORCH_CHECK(dst_row.numel() == P, "src_row and dst_row must have the same number of entries");
+  TORCH_CHECK(w_src.dim() == 2 && w_src.size(1) == d_in && w_dst.dim() == 2 && w_dst.size(0) == D &&
+                  w_dst.size(1) == d_in,
+              "w_src / w_dst must be [D, d]");
+  TORCH_CHECK(w_out.numel() == D && b_out.numel() == 1, "w_out must have D entries and b_out one");
+  same_device(z, {&loo_z, &count, &src_row, &dst_row, &w_src, &w_dst, &w_out, &b_out});
+  const float* bs = opt_ptr(b_src, z, D, "b_src");
+  const float* bd = opt_ptr(b_dst, z, D, "b_dst");
+  const c10::OptionalDeviceGuard guard(z.device());
+  at::Tensor base = at::empty({P}, z.options()), sl = at::empty({P, K}, z.options()), dl = at::empty({P, K}, z.options());
+  at::Tensor status = at::zeros({1}, z.options().dtype(at::kLong));
+  const size_t nb = tgnx_link_predictor_loo_ws_bytes(n, K, P, d_in, D);
+  at::Tensor ws = at::empty({(int64_t)nb}, z.options().dtype(at::kByte));
+  check_rc(tgnx_link_predictor_loo(n, K, P, d_in, D, z.data_ptr<float>(), loo_z.data_ptr<float>(),
+                                   count.data_ptr<int32_t>(), src_row.data_ptr<int64_t>(), dst_row.data_ptr<int64_t>(),
+                                   w_src.data_ptr<float>(), bs, w_dst.data_ptr<float>(), bd, w_out.data_ptr<float>(),
+                                   b_out.data_ptr<float>(), base.data_ptr<float>(), sl.data_ptr<float>(),
+                                   dl.data_ptr<float>(), status.data_ptr<int64_t>(), ws.data_ptr(), nb, cur_stream()),
+           "tgnx_link_predictor_loo");
+  return {base, sl, dl, status};
+}
+
 void attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const c10::optional<at::Tensor>& e,
                const at::Tensor& indptr, int64_t heads) {
   dev_tensor(q, at::kFloat, "q");
@@ -1271,6 +1313,9 @@ TORCH_LIBRARY(tgnx, m) {
         "Tensor w_out, Tensor b_out, Tensor target, int n_count, Tensor? cand_key, Tensor? src_key, Tensor? excl_ptr, "
         "Tensor? excl_key) -> (Tensor, Tensor, Tensor, Tensor)",
         &predictor_rank);
+  m.def("predictor_loo(Tensor z, Tensor loo_z, Tensor count, Tensor src_row, Tensor dst_row, Tensor w_src, "
+        "Tensor? b_src, Tensor w_dst, Tensor? b_dst, Tensor w_out, Tensor b_out) -> (Tensor, Tensor, Tensor, Tensor)",
+        &predictor_loo);
   m.def("predictor_bwd(Tensor dout, Tensor z_src, Tensor z_dst, Tensor w_src, Tensor? b_src, Tensor w_dst, "
         "Tensor? b_dst, Tensor w_out, Tensor b_out, bool sigmoid, int[] need) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",

@@ -7,6 +7,7 @@ from tgnx.tgn_epoch import grow_nodes, observe_grow  # noqa: F401
 from tgnx.tgn_epoch import embedding_table  # noqa: F401
 from tgnx.tgn_epoch import similar  # noqa: F401
 from tgnx.tgn_epoch import forget  # noqa: F401
+from tgnx.tgn_epoch import explain, explain_recommendations  # noqa: F401
 from tgnx.tgn_epoch import edgebank, tgb_negatives  # noqa: F401
 from tgnx.nodeprop import test_node, train_node  # noqa: F401
 from tgnx.nn import NodePredictor  # noqa: F401

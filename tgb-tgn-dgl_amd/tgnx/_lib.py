@@ -61,6 +61,7 @@ SIGNATURES = {
     "tgnx_tgn_eval_step_resident": (ctypes.c_int, [P, P, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_u64, P, c_vp]),
     "tgnx_tgn_embed_max_nodes": (c_i64, [P]),
     "tgnx_tgn_embed": (ctypes.c_int, [P, P, P, c_i64, P, P, c_vp]),
+    "tgnx_tgn_explain": (ctypes.c_int, [P, P, P, c_i64, c_i32, P, P, P, P, P, P, P, c_vp]),
     "tgnx_tgn_observe_step": (ctypes.c_int, [P, P, c_vp]),
     # the embedding table's stale-row bookkeeping (tgnx_embtab.hip) and its refresh
     "tgnx_embtab_touch": (ctypes.c_int, [P, P, c_i64, c_i64, P, c_vp]),
@@ -126,6 +127,9 @@ SIGNATURES = {
     "tgnx_link_predictor_rank_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "tgnx_link_predictor_rank": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, c_i64, P, P, P, P, P,
                                                 c_i64, P, P, P, P, P, c_sz, c_vp]),
+    "tgnx_link_predictor_loo_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "tgnx_link_predictor_loo": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                               P, P, P, c_sz, c_vp]),
     "tgnx_embed_knn_ws_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i32]),
     "tgnx_embed_knn": (ctypes.c_int, [c_i64, c_i64, c_i64, P, P, c_i32, c_i32, P, P, P, P, c_i64, P, P, P, P, c_sz,
                                       c_vp]),

@@ -221,6 +221,13 @@ class LinkPredictor(nn.Module):
         return ops.link_rank(z_src, z_cand, self.lin_src.weight, self.lin_src.bias, self.lin_dst.weight,
                              self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias, target, **kw)
 
+    def loo(self, z, loo_z, count, src_row, dst_row):
+        """Leave-one-out logits of the pairs (z[src_row[p]], z[dst_row[p]]): (base [P], src_logit [P, K], dst_logit
+        [P, K], status [1]) — ops.link_loo with this predictor's parameters; z [n, d], loo_z [n, K, d] and count [n]
+        per unique node.  No autograd."""
+        return ops.link_loo(z, loo_z, count, src_row, dst_row, self.lin_src.weight, self.lin_src.bias,
+                            self.lin_dst.weight, self.lin_dst.bias, self.lin_final.weight, self.lin_final.bias)
+
 
 class NodePredictor(nn.Module):
     """modules/decoder.py:30-41: out(relu(lin_node(node_embed))), logits [M, out_dim] (no softmax, as the reference);

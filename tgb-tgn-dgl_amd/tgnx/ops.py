@@ -10,7 +10,8 @@ tcsr_sample (TGL t-CSR, utils.py:73), gemm_f32 (MFMA fp32 GEMM), and the TGN mod
 gru_update (TGNMemory's GRUCell / RNNCell, memory_module.py:70-78), predictor (LinkPredictor decoder.py:12-27;
 EdgePredictor model_utils.py:165-195), predictor_topk (LinkPredictor over all pairs with the top-k selection fused
 in, csrc/tgnx_topk.hip; `link_topk` below; predictor_topk_filtered / predictor_topk_lists: the same with per-source
-exclusions by key / a candidate list per source), embed_knn (nearest neighbours in embedding space, dot or cosine, on the
+exclusions by key / a candidate list per source; predictor_loo: the logit of explicit pairs with one side's embedding
+replaced by each of its leave-one-out rows, csrc/tgnx_explain.hip; `link_loo` below), embed_knn (nearest neighbours in embedding space, dot or cosine, on the
 f32 MFMA with the same selection and exclusions, csrc/tgnx_knn.hip; `embed_knn` below) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
 emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function), time_encode (TimeEncoder)
 and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
@@ -33,7 +34,7 @@ import torch
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "predictor_topk", "edge_attn_fwd", "edge_attn_bwd",
-       "predictor_topk_filtered", "predictor_topk_lists", "predictor_rank", "embed_knn",
+       "predictor_topk_filtered", "predictor_topk_lists", "predictor_rank", "predictor_loo", "embed_knn",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
        "time_embedding_bwd", "msg_agg_last_bwd", "msg_agg_mean_bwd",
@@ -268,6 +269,43 @@ def link_rank(z_src, z_cand, w_src, b_src, w_dst, b_dst, w_out, b_out, target, n
         z_cand.size(0) if n_count is None else int(n_count), key(cand_key), key(src_key), ptr, keys)
     rank = torch.add(gt, eq.double(), alpha=0.5).add_(1.0)
     return rank.masked_fill_(torch.isnan(tlogit), float("nan")), gt, eq, n, tlogit
+
+
+def check_link_loo_args(z_shape, loo_shape, n_count, n_src, n_dst) -> tuple:
+    """The shapes ops.link_loo takes: z [n, d], loo_z [n, K, d] with 1 <= K <= 64, count [n], src_row and dst_row of
+    one length P.  Returns (n, K, P); ValueError otherwise.  (Host arithmetic only: no device, no library.)"""
+    z_shape, loo_shape = tuple(z_shape), tuple(loo_shape)
+    if len(z_shape) != 2 or len(loo_shape) != 3 or loo_shape[0] != z_shape[0] or loo_shape[2] != z_shape[1]:
+        raise ValueError(f"link_loo: z must be [n, d] and loo_z [n, K, d], got {z_shape} and {loo_shape}")
+    n, K = z_shape[0], loo_shape[1]
+    if not 1 <= K <= 64:
+        raise ValueError(f"link_loo: loo_z must hold 1 <= K <= 64 rows per node, got {K}")
+    if n_count != n:
+        raise ValueError(f"link_loo: count must have n = {n} entries, got {n_count}")
+    if n_src != n_dst:
+        raise ValueError(f"link_loo: {n_src} source rows for {n_dst} destination rows")
+    return n, K, n_src
+
+
+@torch.no_grad()
+def link_loo(z, loo_z, count, src_row, dst_row, w_src, b_src, w_dst, b_dst, w_out, b_out):
+    """Leave-one-out link logits (tgnx_link_predictor_loo, csrc/tgnx_explain.hip).  z [n, d] and loo_z [n, K, d] hold
+    the embedding and the K leave-one-out embeddings of n unique nodes (TgnEngine's tgnx_tgn_explain outputs), count
+    [n] how many of a node's K rows exist; pair p names rows src_row[p] and dst_row[p].  Returns (base [P], src_logit
+    [P, K], dst_logit [P, K], status [1] int64): the pair's LinkPredictor logit, the logit with the source's embedding
+    replaced by its row j (the destination at its full embedding), and the converse — each side varied alone also when
+    both name one node; an entry past the varied node's count holds base's bits.  Every unique row is projected once
+    (four GEMMs), then each logit is one sequential fma chain: its bits do not depend on the order of the pairs.  A row
+    index outside [0, n) gives NaN outputs for its pair and status = 1; it is never dereferenced, and no host read
+    checks it here.  Inference only: no autograd."""
+    dev = z.device
+    idx = lambda t: torch.as_tensor(t).to(dev, torch.long).contiguous().view(-1)  # noqa: E731
+    c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+    src_row, dst_row = idx(src_row), idx(dst_row)
+    count = torch.as_tensor(count).to(dev, torch.int32).contiguous().view(-1)
+    check_link_loo_args(z.shape, loo_z.shape, count.numel(), src_row.numel(), dst_row.numel())
+    return load().predictor_loo(c(z), c(loo_z), count, src_row, dst_row, c(w_src), c(b_src), c(w_dst), c(b_dst),
+                                c(w_out).view(-1), c(b_out).view(-1))
 
 
 KNN_METRICS = {"dot": 0, "cosine": 1}     # TGNX_KNN_DOT / TGNX_KNN_COSINE

@@ -454,6 +454,24 @@ def check_observe_args(start: int, B: int, max_batch: int, num_events: int, worl
         raise ValueError(f"observe: rows [{start}, {start + B}) outside the event table ({num_events} events)")
 
 
+EXPLAIN_MODES = {"slot": 0, "neighbour": 1}      # TGNX_EXPLAIN_SLOT / TGNX_EXPLAIN_NEIGHBOUR
+
+
+def check_explain_args(by, n_src: int, n_dst: int, layers: int = 1, world: int = 1) -> int:
+    """explain()'s arguments: the removal set's name, one destination per source, a 1-hop engine on one device.
+    Returns the C ABI's mode code."""
+    if by not in EXPLAIN_MODES:
+        raise ValueError(f"explain: by must be one of {sorted(EXPLAIN_MODES)}, got {by!r}")
+    if n_src != n_dst:
+        raise ValueError(f"explain: {n_src} sources for {n_dst} destinations")
+    if layers == 2:
+        raise NotImplementedError("explain: leave-one-out effects are built for the 1-hop embedding (layers = 1): at 2 "
+                                  "hops removing an edge also changes the node's own hop-1 row; attention() works")
+    if world > 1:
+        raise NotImplementedError("explain: one device only (world > 1: a data-parallel engine)")
+    return EXPLAIN_MODES[by]
+
+
 def check_compact_args(num_events: int, upto=None, capacity=None, world: int = 1) -> int:
     """The resolved `upto` of compact_events (default num_events), or ValueError: one device, 0 <= upto <= num_events,
     capacity (when given) at least 1."""
@@ -1707,6 +1725,97 @@ class TgnEngine:
         if n == 0:
             return zs.new_empty(0)
         return ops.link_predictor(zs.contiguous(), zd.contiguous(), *self._link_weights(), sigmoid=True).view(-1)
+
+    # ------------------------------------------------------------------ why a score is what it is
+    def _explain_nodes(self, nodes, mode: int, loo: bool, validate: bool, what: str) -> dict:
+        """tgnx_tgn_explain over a node list, in chunks of embed_capacity(): z [n, D], count [n] int32, event /
+        neighbour [n, K] int64, alpha [n, K, 2] and (loo) loo_z [n, K, D]."""
+        self._settle()
+        nodes = self._ids(nodes)
+        n, N, K, D = nodes.numel(), self.cfg.num_nodes, self.cfg.ring, self.cfg.mem_dim
+        if validate and n and bool(((nodes < 0) | (nodes >= N)).any()):
+            raise ValueError(f"{what}: node ids must be in [0, {N})")
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = dict(z=torch.empty(n, D, **f32), count=torch.empty(n, dtype=torch.int32, device=self.dev),
+                   event=torch.empty(n, K, dtype=torch.long, device=self.dev),
+                   neighbour=torch.empty(n, K, dtype=torch.long, device=self.dev), alpha=torch.empty(n, K, 2, **f32))
+        if loo:
+            out["loo_z"] = torch.empty(n, K, D, **f32)
+        cap = self.embed_capacity()
+        if cap <= 0:
+            raise RuntimeError(f"tgnx_tgn_embed_max_nodes: {_lib.lib().tgnx_last_error().decode()}")
+        bad = torch.zeros(1, dtype=torch.long, device=self.dev)
+        b = self._buffers(0)
+        at = lambda t, a: t.data_ptr() + a * (t.numel() // max(n, 1)) * t.element_size()  # noqa: E731
+        for a in range(0, n, cap):
+            _lib.call("tgnx_tgn_explain", ctypes.byref(self.cfg), ctypes.byref(b), nodes.data_ptr() + a * 8,
+                      min(cap, n - a), mode, at(out["z"], a), at(out["count"], a), at(out["event"], a),
+                      at(out["neighbour"], a), at(out["alpha"], a), at(out["loo_z"], a) if loo else 0, _p(bad),
+                      self._stream())
+        if n:
+            self.check()
+        out["n_invalid"] = bad
+        return out
+
+    @torch.no_grad()
+    def attention(self, nodes, validate: bool = True) -> dict:
+        """What each node's embedding attends over at the current stream state: a dict with, per listed node, `count`
+        [n] (the valid slots of its ring row), `neighbour` and `event` [n, K] (the slot's neighbour node and event row,
+        in the sampler's order, -1 past count), `t` [n, K] (the event table's time of the slot, 0 past count), `alpha`
+        [n, K, 2] (the eval-mode attention weight per head of the node's own TransformerConv softmax, 0 past count;
+        at layers = 2 the root level's, conv2) and `z` [n, D], bit for bit embed()'s rows.  Read-only and chunked as
+        embed() is (tgnx_tgn_explain without the leave-one-out rows).  validate: as embed(); without it an id out of
+        range gets zero rows, count 0 and -1 slots, and is counted in `n_invalid` [1]."""
+        o = self._explain_nodes(nodes, 0, False, validate, "attention")
+        o["t"] = self._slot_times(o["event"])
+        return o
+
+    def _slot_times(self, event) -> torch.Tensor:
+        """The event table's time of each slot's event row; 0 where the slot is padding (-1)."""
+        return torch.where(event >= 0, self._tab[2][event.clamp(min=0)], torch.zeros((), device=self.dev))
+
+    @torch.no_grad()
+    def explain(self, src, dst, by: str = "slot") -> dict:
+        """Which past interaction moved the link score of each pair (src[i], dst[i]), and by how much.  A node's
+        embedding is its memory row plus one attention over the at most `ring` interactions of its ring row, so the
+        effect of an interaction is exact: the same forward with that slot absent (tgnx_tgn_explain recomputes the
+        softmax over the remaining slots; ops.link_loo scores every pair with one side's embedding replaced).
+        Returns a dict: `logit`, `prob` [P]; `src_effect`, `dst_effect` [P, K] = logit - the logit without S_j
+        (positive: the interaction raised the score; 0 past the node's count), where S_j is slot j (by="slot") or every
+        slot naming slot j's neighbour (by="neighbour": repeat interactions removed together; `src_lead` / `dst_lead`
+        [P, K] then mark the first slot of each neighbour group, the others repeat its effect); and per side
+        `*_neighbour`, `*_event` [P, K] (-1 past count), `*_t`, `*_alpha` (mean over heads) [P, K], `*_count` [P].
+        unique(src ∪ dst) is embedded once (in chunks beyond embed_capacity()): `nodes` [n] are those ids, `z` [n, D]
+        (embed()'s rows, bit for bit) and `loo_z` [n, K, D] their embeddings and leave-one-out embeddings, and
+        `src_row` / `dst_row` [P] each pair's rows among them.  Read-only as embed() is.  Built for
+        the 1-hop embedding on one device: layers = 2 (removing an edge also changes the node's own hop-1 row) and a
+        data-parallel engine raise NotImplementedError; attention() works at 2 hops."""
+        from . import ops
+        src, dst = self._ids(src), self._ids(dst)
+        mode = check_explain_args(by, src.numel(), dst.numel(), 2 if self.cfg.layers == 2 else 1, self.world)
+        N, P = self.cfg.num_nodes, src.numel()
+        if P and bool(((src < 0) | (src >= N) | (dst < 0) | (dst >= N)).any()):
+            raise ValueError(f"explain: node ids must be in [0, {N})")
+        uniq, inv = torch.unique(torch.cat([src, dst]), return_inverse=True)
+        o = self._explain_nodes(uniq, mode, True, False, "explain")
+        rows = (inv[:P].contiguous(), inv[P:].contiguous())
+        base, sl, dl, _ = ops.link_loo(o["z"], o["loo_z"], o["count"], rows[0], rows[1], *self._link_weights())
+        ev = o["event"]
+        t = self._slot_times(ev)
+        alpha = o["alpha"].mean(-1)
+        out = dict(logit=base, prob=torch.sigmoid(base), src_effect=base.view(-1, 1) - sl,
+                   dst_effect=base.view(-1, 1) - dl, nodes=uniq, z=o["z"], loo_z=o["loo_z"], src_row=rows[0],
+                   dst_row=rows[1])
+        nb = o["neighbour"]
+        for side, r in zip(("src", "dst"), rows):
+            out[f"{side}_neighbour"], out[f"{side}_event"], out[f"{side}_t"] = nb[r], ev[r], t[r]
+            out[f"{side}_alpha"], out[f"{side}_count"] = alpha[r], o["count"][r]
+        if mode == 1:  # first slot of each neighbour group: no earlier slot of the row names the same neighbour
+            K = nb.size(1)
+            same = (nb.unsqueeze(2) == nb.unsqueeze(1)) & torch.ones(K, K, dtype=torch.bool, device=self.dev).tril(-1)
+            lead = (nb >= 0) & ~same.any(2)
+            out["src_lead"], out["dst_lead"] = lead[rows[0]], lead[rows[1]]
+        return out
 
     @torch.no_grad()
     def rank(self, src, dst, candidates=None, return_scores: bool = False, *, exclude_seen: bool = False,

@@ -22,6 +22,9 @@ updates the stores, the memory and the ring in eval order.
       per_source): the same with per-source exclusions or per-source candidate lists (TgnEngine.recommend_filtered)
   similar(model, neighbor_loader, nodes, k, candidates=None, *, metric, exclude_self, exclude_seen, exclude, cached)
       -> (score [Q, k], node_ids [Q, k]): every node's k nearest neighbours in embedding space (TgnEngine.similar)
+  explain(model, src, dst, by="slot") -> dict: per pair the logit and, per side, the ring slots the embedding attends
+      over with their attention weight and leave-one-out effect on the logit (TgnEngine.explain; 1 hop, read-only);
+      explain_recommendations(model, src, k, **filters): recommend_filtered, then explain of the (src, top-k) pairs
   embedding_table(model, neighbor_loader) -> [N, D]: the current embeddings of every node, kept incrementally
       (TgnEngine.embedding_table); recommend_filtered / rank_stream take cached=True to read it
   observe(model, neighbor_loader, src, dst, t, msg, batch=None) -> (start, n): new interactions appended to the event
@@ -250,6 +253,39 @@ def similar(model, neighbor_loader, nodes, k, candidates=None, *, metric="cosine
         eng.enable_embedding_table()
     return eng.similar(nodes, k, candidates=candidates, metric=metric, exclude_self=exclude_self,
                        exclude_seen=exclude_seen, exclude=exclude, cached=cached)
+
+
+def _attached_engine(model, what):
+    """The engine train() / test() attached to the model (its own neighbor_loader: the calls that take none)."""
+    eng = getattr(_owner(model), "_tgnx_engine", None)
+    if eng is None:
+        raise RuntimeError(f"tgnx {what}: no engine bound to this model yet (run train() or test() first: they bind "
+                           "the event table)")
+    return eng
+
+
+@torch.no_grad()
+def explain(model, src, dst, by="slot"):
+    """Why the model scores the pairs (src[i], dst[i]) as it does, with the engine train() / test() attached to the
+    model: TgnEngine.explain's dict — the logit, and per side the ring slots the embedding attended over with their
+    attention weight and their leave-one-out effect on the logit (by="slot": one slot removed; by="neighbour": every
+    slot of that neighbour).  Read-only; switches the memory to eval first as recommend() does (one flush)."""
+    eng = _attached_engine(model, "explain")
+    if eng._mode_train:
+        eng.flush()
+        eng._mode_train = False
+    return eng.explain(src, dst, by=by)
+
+
+@torch.no_grad()
+def explain_recommendations(model, src, k, by="slot", **filters):
+    """recommend_filtered(src, k, **filters) followed by explain() of the (source, recommended node) pairs.  Returns
+    (val [Q, k], node_ids [Q, k], pair [n_pairs, 2] = (row into src, column of node_ids) of every explained pair, the
+    explain() dict over those pairs); the -1 padding of node_ids (k beyond the candidate count) is skipped."""
+    eng = _attached_engine(model, "explain_recommendations")
+    val, ids = recommend_filtered(model, eng.loader, src, k, **filters)[:2]
+    pair = (ids >= 0).nonzero()
+    return val, ids, pair, eng.explain(eng._ids(src)[pair[:, 0]], ids[pair[:, 0], pair[:, 1]], by=by)
 
 
 @torch.no_grad()
