@@ -1071,7 +1071,7 @@ int tgnx_embed_knn(int64_t n_q, int64_t n_cand, int64_t D, const float* z_q, con
  * q [n_dst, H*C]), per head h: a_p = q_i·(k_p + e_p) / sqrt(C), α = softmax over i's edges (max subtracted,
  * + 1e-16 in the denominator), out_i = Σ_p α_p (v_p + e_p) (the root weight / skip is the caller's Linear).
  * e may be NULL (no edge features).  alpha [E, H] is written.  1 <= heads <= 8, heads * C <= 256.  indptr is
- * clamped to [0, n_edges].  No attention dropout (eval, or dropout 0).
+ * clamped to [0, n_edges].  No attention dropout (eval, or dropout 0; tgnx_edge_attn_drop_fwd below has it).
  * Backward: dq [n_dst, H*C], dk / dv / de [E, H*C] (de = dk + dv, needed only with e) from dout and alpha.
  * indptr need not span all n_edges rows.  An edge row that no destination owns (a row before indptr[0] or from
  * indptr[n_dst] on, indptr non-decreasing; every row when n_dst == 0) takes part in nothing: both calls write
@@ -1082,6 +1082,32 @@ int tgnx_edge_attn_fwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t ch
 int tgnx_edge_attn_bwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* dout,
                        const float* q, const float* k, const float* v, const float* e, const int64_t* indptr,
                        const float* alpha, float* dq, float* dk, float* dv, float* de, void* stream);
+
+/* The same attention with attention dropout, in PyG's order (softmax, then dropout on α):
+ *   out_i = Σ_p (α_p m_p)(v_p + e_p),   m[p,h] = keep32(drop_base(seed, stream_id, dkey_i, ekey_p), h, p, inv)
+ *   dkey_i = dst_key ? dst_key[i] : i,  ekey_p = edge_key ? edge_key[p] : p  (full 64-bit keys),  inv = 1 / (1 - p)
+ * drop_base / keep32 are the counter-based hash of csrc/tgnx_math.h (m is 0 or inv).  alpha [E, H] receives the
+ * softmax BEFORE dropout (PyG's _alpha); the backward takes that alpha and recomputes the mask from (p, seed,
+ * stream_id, keys), so no mask is stored:
+ *   dα_p = m_p (dout_i·(v_p + e_p)),  g_p = α_p (dα_p − Σ α dα) / sqrt(C),  dq_i = Σ g_p (k_p + e_p),
+ *   dk_p = g_p q_i,  dv_p = α_p m_p dout_i,  de_p = dk_p + dv_p.
+ * A (destination, head) that loses every edge gives a zero head block in out and contributes zeros; nothing is
+ * divided by a kept count.  p must be finite with 0 <= p < 1 (TGNX_EINVAL before any launch otherwise); p = 0 gives
+ * the bits of tgnx_edge_attn_fwd / _bwd.  dst_key [n_dst] and edge_key [n_edges] are optional (NULL: the row
+ * numbers).  Sizes, indptr clamping and the rows no destination owns are as for the pair above.  No atomics, no
+ * workspace, no host synchronisation: graph-capturable, run-to-run identical.
+ * With stream_id = 7 (the engine's conv; 9 for conv2), dst_key = the centres' node ids, edge_key = the edges' event
+ * ids and seed = a batch's ctl[TGNX_CTL_SEED], the mask is the one tgnx_tgn_train_step draws for that batch. */
+int tgnx_edge_attn_drop_fwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* q,
+                            const float* k, const float* v, const float* e, const int64_t* indptr, float* out,
+                            float* alpha, float p, uint64_t seed, uint64_t stream_id,
+                            const int64_t* dst_key /* optional [n_dst] */,
+                            const int64_t* edge_key /* optional [n_edges] */, void* stream);
+int tgnx_edge_attn_drop_bwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* dout,
+                            const float* q, const float* k, const float* v, const float* e, const int64_t* indptr,
+                            const float* alpha, float* dq, float* dk, float* dv, float* de, float p, uint64_t seed,
+                            uint64_t stream_id, const int64_t* dst_key /* optional [n_dst] */,
+                            const int64_t* edge_key /* optional [n_edges] */, void* stream);
 
 /* ---------------------------------------------------------------- per-operator backward (csrc/tgnx_ops_bwd.hip)
  * What torch autograd needs to train a composition of the operators above (tgnx/ops.py, tgnx/nn.py).  Same

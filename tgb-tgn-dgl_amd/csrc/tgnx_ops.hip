@@ -8,6 +8,7 @@
 //   tgnx_link_predictor   LinkPredictor                     modules/decoder.py:12-27
 //                         EdgePredictor (tile pairing)      model_utils.py:165-195
 //   tgnx_edge_attn_fwd/bwd  TransformerConv's attention     modules/emb_module.py:21-29 (PyG TransformerConv)
+//   tgnx_edge_attn_drop_fwd/bwd  the same with attention dropout (TransformerConv(dropout=0.1), emb_module.py:21)
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -16,6 +17,7 @@
 #include <algorithm>
 
 #include "tgnx_common.h"
+#include "tgnx_math.h"
 
 using namespace tgnx;
 
@@ -194,7 +196,38 @@ __global__ void __launch_bounds__(OPS_BLOCK) pred_rows(int64_t n_src, int64_t M,
 // subtracted, + 1e-16 in the denominator, as torch_geometric.utils.softmax); out_i = Σ_p α_p (v_p + e_p).
 // A wave per destination; lane owns channels x = lane + 64 r (r < NR), head x / C; per-head dot products are
 // masked wave sums.  The scores are recomputed in each of the three passes (max, denominator, α and the
-// weighted sum) rather than written and re-read.  Attention dropout is not applied (eval / dropout 0).
+// weighted sum) rather than written and re-read.
+//
+// Attention dropout (the DROP instantiations; tgnx_edge_attn_drop_fwd / _bwd) follows PyG's order, softmax and then
+// dropout on α: out_i = Σ_p (α_p m_p)(v_p + e_p) with m[p,h] = keep32(drop_base(seed, stream, dkey_i, ekey_p), h)
+// (tgnx_math.h: 0 or 1 / (1 - p_drop)), dkey_i = dst_key ? dst_key[i] : i, ekey_p = edge_key ? edge_key[p] : p.
+// alpha still receives the softmax before dropout; the backward recomputes the mask from the same arguments, so
+// nothing but α is saved.  The keys are made wave-uniform (v_readfirstlane) before they are hashed: the four
+// mix64 of drop_base run once per edge per pass on the scalar unit, and a head's keep32 is one scalar fmix32.
+// A (destination, head) whose edges are all dropped just sums zeros: there is no division by a kept count.
+struct AttnDrop {
+  float p, inv;           // drop probability and 1 / (1 - p)
+  uint64_t seed, stream;
+  const int64_t* dst_key;   // optional [n_dst]
+  const int64_t* edge_key;  // optional [E]
+};
+
+__device__ __forceinline__ uint64_t wave_uniform_u64(uint64_t x) {  // x is the same in every lane: move it to SGPRs
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t attn_dst_key(const AttnDrop& d, int64_t i) {
+  return wave_uniform_u64((uint64_t)(d.dst_key ? d.dst_key[i] : i));
+}
+// m[p, h] for h < H (wave-uniform), the rest 0
+__device__ __forceinline__ void attn_keep(const AttnDrop& d, uint64_t dkey, int64_t p, int H, float* m) {
+  const uint64_t ekey = wave_uniform_u64((uint64_t)(d.edge_key ? d.edge_key[p] : p));
+  const uint32_t base = drop_base(d.seed, d.stream, dkey, ekey);
+#pragma unroll
+  for (int h = 0; h < HMAX; ++h) m[h] = h < H ? keep32(base, (uint32_t)h, d.p, d.inv) : 0.f;
+}
+
 template <int NR>
 struct AttnRow {
   float q[NR];
@@ -244,10 +277,11 @@ __device__ __forceinline__ void edge_range(const int64_t* indptr, int64_t i, int
   e = min(max(indptr[i + 1], b), E);
 }
 
-template <int NR>
+template <int NR, bool DROP>
 __global__ void __launch_bounds__(OPS_BLOCK) attn_fwd(int64_t n_dst, int64_t E, int H, int C, const float* q,
                                                       const float* k, const float* v, const float* e,
-                                                      const int64_t* indptr, float* out, float* alpha) {
+                                                      const int64_t* indptr, float* out, float* alpha,
+                                                      AttnDrop drop) {
   const int64_t i = blockIdx.x * (int64_t)WAVES + (threadIdx.x >> 6);
   if (i >= n_dst) return;
   const int lane = threadIdx.x & 63, HC = H * C;
@@ -276,6 +310,8 @@ __global__ void __launch_bounds__(OPS_BLOCK) attn_fwd(int64_t n_dst, int64_t E, 
   float acc[NR];
 #pragma unroll
   for (int r = 0; r < NR; ++r) acc[r] = 0.f;
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = attn_dst_key(drop, i);
   for (int64_t p = b; p < en; ++p) {
     attn_scores<NR>(row, k, e, p, HC, H, sqrt_c, lane, s);
     float a[HMAX];
@@ -286,7 +322,13 @@ __global__ void __launch_bounds__(OPS_BLOCK) attn_fwd(int64_t n_dst, int64_t E, 
 #pragma unroll
       for (int h = 1; h < HMAX; ++h)
         if (lane == h) al = a[h];
-      alpha[p * H + lane] = al;
+      alpha[p * H + lane] = al;  // the softmax, before dropout
+    }
+    if constexpr (DROP) {
+      float m[HMAX];
+      attn_keep(drop, dkey, p, H, m);
+#pragma unroll
+      for (int h = 0; h < HMAX; ++h) a[h] *= m[h];
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
@@ -309,6 +351,8 @@ __global__ void __launch_bounds__(OPS_BLOCK) attn_fwd(int64_t n_dst, int64_t E, 
 // Backward of attn_fwd given dout [n_dst, H*C] and the forward's α [E, H]:
 //   dα_p = dout_i · (v_p + e_p) per head;  ds_p = α_p (dα_p − Σ_p' α_p' dα_p');  g_p = ds_p / sqrt(C)
 //   dq_i = Σ_p g_p (k_p + e_p);  dk_p = g_p q_i;  dv_p = α_p dout_i;  de_p = dk_p + dv_p
+// DROP: the product above is the gradient of the dropped weight, dã_p; dα_p = m_p dã_p enters S and g, and
+// dv_p = α_p m_p dout_i (the mask recomputed per edge in both passes, as in the forward).
 template <int NR>
 __device__ __forceinline__ void attn_dalpha(const float* dout_r, const float* v, const float* e, int64_t p, int HC,
                                             int H, const AttnRow<NR>& row, int lane, float* da) {
@@ -333,11 +377,11 @@ __device__ __forceinline__ void attn_dalpha(const float* dout_r, const float* v,
   }
 }
 
-template <int NR>
+template <int NR, bool DROP>
 __global__ void __launch_bounds__(OPS_BLOCK) attn_bwd(int64_t n_dst, int64_t E, int H, int C, const float* dout,
                                                       const float* q, const float* k, const float* v,
                                                       const float* e, const int64_t* indptr, const float* alpha,
-                                                      float* dq, float* dk, float* dv, float* de) {
+                                                      float* dq, float* dk, float* dv, float* de, AttnDrop drop) {
   const int64_t i = blockIdx.x * (int64_t)WAVES + (threadIdx.x >> 6);
   if (i >= n_dst) return;
   const int lane = threadIdx.x & 63, HC = H * C;
@@ -348,11 +392,19 @@ __global__ void __launch_bounds__(OPS_BLOCK) attn_bwd(int64_t n_dst, int64_t E, 
   for (int r = 0; r < NR; ++r) dout_r[r] = row.ok[r] ? dout[i * HC + lane + 64 * r] : 0.f;
   int64_t b, en;
   edge_range(indptr, i, E, b, en);
-  float S[HMAX], da[HMAX];
+  float S[HMAX], da[HMAX], m[HMAX];
 #pragma unroll
   for (int h = 0; h < HMAX; ++h) S[h] = 0.f;
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = attn_dst_key(drop, i);
   for (int64_t p = b; p < en; ++p) {
     attn_dalpha<NR>(dout_r, v, e, p, HC, H, row, lane, da);
+    if constexpr (DROP) {
+      attn_keep(drop, dkey, p, H, m);
+#pragma unroll
+      for (int h = 0; h < HMAX; ++h)
+        if (h < H) da[h] *= m[h];
+    }
 #pragma unroll
     for (int h = 0; h < HMAX; ++h)
       if (h < H) S[h] += alpha[p * H + h] * da[h];
@@ -362,11 +414,18 @@ __global__ void __launch_bounds__(OPS_BLOCK) attn_bwd(int64_t n_dst, int64_t E, 
   for (int r = 0; r < NR; ++r) dq_acc[r] = 0.f;
   for (int64_t p = b; p < en; ++p) {
     attn_dalpha<NR>(dout_r, v, e, p, HC, H, row, lane, da);
+    if constexpr (DROP) {
+      attn_keep(drop, dkey, p, H, m);
+#pragma unroll
+      for (int h = 0; h < HMAX; ++h)
+        if (h < H) da[h] *= m[h];
+    }
     float g[HMAX], al[HMAX];
 #pragma unroll
     for (int h = 0; h < HMAX; ++h) {
       al[h] = h < H ? alpha[p * H + h] : 0.f;
       g[h] = h < H ? __fdiv_rn(al[h] * (da[h] - S[h]), sqrt_c) : 0.f;
+      if constexpr (DROP) al[h] *= m[h];  // from here on al is the dropped weight (dv)
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
@@ -445,12 +504,78 @@ int attn_dispatch(int HC, int64_t n_dst, hipStream_t s, A... args) {
 }
 template <int NR>
 struct FwdK {
-  static constexpr auto fn = attn_fwd<NR>;
+  static constexpr auto fn = attn_fwd<NR, false>;
 };
 template <int NR>
 struct BwdK {
-  static constexpr auto fn = attn_bwd<NR>;
+  static constexpr auto fn = attn_bwd<NR, false>;
 };
+template <int NR>
+struct FwdDropK {
+  static constexpr auto fn = attn_fwd<NR, true>;
+};
+template <int NR>
+struct BwdDropK {
+  static constexpr auto fn = attn_bwd<NR, true>;
+};
+
+// The two entry-point pairs share their checks and launches: `drop` null = the plain ops.
+int attn_fwd_launch(const char* name, int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels,
+                    const float* q, const float* k, const float* v, const float* e, const int64_t* indptr,
+                    float* out, float* alpha, const AttnDrop* drop, void* stream) {
+  TGNX_CHECK_ARG(n_dst >= 0 && n_edges >= 0 && heads > 0 && heads <= HMAX && channels > 0,
+                 "%s: bad sizes (1 <= heads <= %d)", name, HMAX);
+  TGNX_CHECK_ARG((int64_t)heads * channels <= 256, "%s: heads * channels must be <= 256", name);
+  TGNX_CHECK_ARG(n_dst == 0 || (q && indptr && out && (n_edges == 0 || (k && v && alpha))), "%s: null pointer",
+                 name);
+  // rows of alpha that no destination owns (all of them without destinations) are zero, not left as they were
+  int rc = attn_zero_launch(n_dst, n_edges, indptr, AttnRows{{alpha, nullptr, nullptr, nullptr}, {heads, 0, 0, 0}},
+                            as_stream(stream));
+  if (rc != TGNX_OK || n_dst == 0) return rc;
+  if (drop)
+    rc = attn_dispatch<FwdDropK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
+                                 (int)channels, q, k, v, e, indptr, out, alpha, *drop);
+  else
+    rc = attn_dispatch<FwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads, (int)channels,
+                             q, k, v, e, indptr, out, alpha, AttnDrop{});
+  if (rc != TGNX_OK) return rc;
+  TGNX_LAUNCH_CHECK("attn_fwd");
+  return TGNX_OK;
+}
+
+int attn_bwd_launch(const char* name, int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels,
+                    const float* dout, const float* q, const float* k, const float* v, const float* e,
+                    const int64_t* indptr, const float* alpha, float* dq, float* dk, float* dv, float* de,
+                    const AttnDrop* drop, void* stream) {
+  TGNX_CHECK_ARG(n_dst >= 0 && n_edges >= 0 && heads > 0 && heads <= HMAX && channels > 0,
+                 "%s: bad sizes (1 <= heads <= %d)", name, HMAX);
+  TGNX_CHECK_ARG((int64_t)heads * channels <= 256, "%s: heads * channels must be <= 256", name);
+  TGNX_CHECK_ARG(n_dst == 0 || (dout && q && indptr && dq && (n_edges == 0 || (k && v && alpha && dk && dv)) &&
+                                (!e || de || !n_edges)),
+                 "%s: null pointer", name);
+  // as the forward: dk / dv / de rows that no destination owns are zero
+  const int HC = heads * channels;
+  int rc = attn_zero_launch(n_dst, n_edges, indptr, AttnRows{{dk, dv, de, nullptr}, {HC, HC, HC, 0}},
+                            as_stream(stream));
+  if (rc != TGNX_OK || n_dst == 0) return rc;
+  if (drop)
+    rc = attn_dispatch<BwdDropK>(HC, n_dst, as_stream(stream), n_dst, n_edges, (int)heads, (int)channels, dout, q, k,
+                                 v, e, indptr, alpha, dq, dk, dv, de, *drop);
+  else
+    rc = attn_dispatch<BwdK>(HC, n_dst, as_stream(stream), n_dst, n_edges, (int)heads, (int)channels, dout, q, k, v,
+                             e, indptr, alpha, dq, dk, dv, de, AttnDrop{});
+  if (rc != TGNX_OK) return rc;
+  TGNX_LAUNCH_CHECK("attn_bwd");
+  return TGNX_OK;
+}
+
+// 0 <= p < 1 and finite (a NaN fails the first comparison); inv as the fused train step forms it
+bool attn_drop_args(float p, uint64_t seed, uint64_t stream_id, const int64_t* dst_key, const int64_t* edge_key,
+                    AttnDrop* d) {
+  if (!(p >= 0.f && p < 1.f)) return false;
+  *d = AttnDrop{p, 1.0f / (1.0f - p), seed, stream_id, dst_key, edge_key};
+  return true;
+}
 
 }  // namespace
 
@@ -567,41 +692,37 @@ int tgnx_link_predictor(int64_t n_src, int64_t M, int64_t d_in, int64_t D, const
 int tgnx_edge_attn_fwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* q,
                        const float* k, const float* v, const float* e, const int64_t* indptr, float* out,
                        float* alpha, void* stream) {
-  TGNX_CHECK_ARG(n_dst >= 0 && n_edges >= 0 && heads > 0 && heads <= HMAX && channels > 0,
-                 "tgnx_edge_attn_fwd: bad sizes (1 <= heads <= %d)", HMAX);
-  TGNX_CHECK_ARG((int64_t)heads * channels <= 256, "tgnx_edge_attn_fwd: heads * channels must be <= 256");
-  TGNX_CHECK_ARG(n_dst == 0 || (q && indptr && out && (n_edges == 0 || (k && v && alpha))),
-                 "tgnx_edge_attn_fwd: null pointer");
-  // rows of alpha that no destination owns (all of them without destinations) are zero, not left as they were
-  int rc = attn_zero_launch(n_dst, n_edges, indptr, AttnRows{{alpha, nullptr, nullptr, nullptr}, {heads, 0, 0, 0}},
-                            as_stream(stream));
-  if (rc != TGNX_OK || n_dst == 0) return rc;
-  rc = attn_dispatch<FwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
-                           (int)channels, q, k, v, e, indptr, out, alpha);
-  if (rc != TGNX_OK) return rc;
-  TGNX_LAUNCH_CHECK("attn_fwd");
-  return TGNX_OK;
+  return attn_fwd_launch("tgnx_edge_attn_fwd", n_dst, n_edges, heads, channels, q, k, v, e, indptr, out, alpha,
+                         nullptr, stream);
 }
 
 int tgnx_edge_attn_bwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* dout,
                        const float* q, const float* k, const float* v, const float* e, const int64_t* indptr,
                        const float* alpha, float* dq, float* dk, float* dv, float* de, void* stream) {
-  TGNX_CHECK_ARG(n_dst >= 0 && n_edges >= 0 && heads > 0 && heads <= HMAX && channels > 0,
-                 "tgnx_edge_attn_bwd: bad sizes (1 <= heads <= %d)", HMAX);
-  TGNX_CHECK_ARG((int64_t)heads * channels <= 256, "tgnx_edge_attn_bwd: heads * channels must be <= 256");
-  TGNX_CHECK_ARG(n_dst == 0 || (dout && q && indptr && dq && (n_edges == 0 || (k && v && alpha && dk && dv)) &&
-                                (!e || de || !n_edges)),
-                 "tgnx_edge_attn_bwd: null pointer");
-  // as the forward: dk / dv / de rows that no destination owns are zero
-  const int HC = heads * channels;
-  int rc = attn_zero_launch(n_dst, n_edges, indptr, AttnRows{{dk, dv, de, nullptr}, {HC, HC, HC, 0}},
-                            as_stream(stream));
-  if (rc != TGNX_OK || n_dst == 0) return rc;
-  rc = attn_dispatch<BwdK>(heads * channels, n_dst, as_stream(stream), n_dst, n_edges, (int)heads,
-                           (int)channels, dout, q, k, v, e, indptr, alpha, dq, dk, dv, de);
-  if (rc != TGNX_OK) return rc;
-  TGNX_LAUNCH_CHECK("attn_bwd");
-  return TGNX_OK;
+  return attn_bwd_launch("tgnx_edge_attn_bwd", n_dst, n_edges, heads, channels, dout, q, k, v, e, indptr, alpha, dq,
+                         dk, dv, de, nullptr, stream);
+}
+
+int tgnx_edge_attn_drop_fwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* q,
+                            const float* k, const float* v, const float* e, const int64_t* indptr, float* out,
+                            float* alpha, float p, uint64_t seed, uint64_t stream_id, const int64_t* dst_key,
+                            const int64_t* edge_key, void* stream) {
+  AttnDrop d;
+  TGNX_CHECK_ARG(attn_drop_args(p, seed, stream_id, dst_key, edge_key, &d),
+                 "tgnx_edge_attn_drop_fwd: p must be finite with 0 <= p < 1");
+  return attn_fwd_launch("tgnx_edge_attn_drop_fwd", n_dst, n_edges, heads, channels, q, k, v, e, indptr, out, alpha,
+                         &d, stream);
+}
+
+int tgnx_edge_attn_drop_bwd(int64_t n_dst, int64_t n_edges, int32_t heads, int32_t channels, const float* dout,
+                            const float* q, const float* k, const float* v, const float* e, const int64_t* indptr,
+                            const float* alpha, float* dq, float* dk, float* dv, float* de, float p, uint64_t seed,
+                            uint64_t stream_id, const int64_t* dst_key, const int64_t* edge_key, void* stream) {
+  AttnDrop d;
+  TGNX_CHECK_ARG(attn_drop_args(p, seed, stream_id, dst_key, edge_key, &d),
+                 "tgnx_edge_attn_drop_bwd: p must be finite with 0 <= p < 1");
+  return attn_bwd_launch("tgnx_edge_attn_drop_bwd", n_dst, n_edges, heads, channels, dout, q, k, v, e, indptr, alpha,
+                         dq, dk, dv, de, &d, stream);
 }
 
 }  // extern "C"

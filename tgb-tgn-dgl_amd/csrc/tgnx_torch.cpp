@@ -22,6 +22,7 @@
 //   gru_update                               TGNMemory.memory_updater GRUCell / RNNCell (memory_module.py:70-78)
 //   predictor                                LinkPredictor (decoder.py:12-27) / EdgePredictor (model_utils.py:165-195)
 //   edge_attn_fwd / edge_attn_bwd            TransformerConv's attention (emb_module.py:21-29, PyG semantics)
+//   edge_attn_drop_fwd / edge_attn_drop_bwd  the same with attention dropout under the engine's counter-based mask
 //   time_encode / time_embedding             TimeEncoder ([ext] PyG) / TimeEmbedding (emb_module.py:32-52)
 //   col_sum, gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd,
 //   msg_agg_mean_bwd                         the backward halves (csrc/tgnx_ops_bwd.hip) behind tgnx/ops.py's
@@ -765,40 +766,121 @@ void attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, co
   }
 }
 
+// attention dropout's arguments (edge_attn_drop_fwd / _bwd): p, the seed and the optional int64 keys
+struct AttnDropArgs {
+  float p;
+  uint64_t seed, stream;
+  const int64_t* dst_key;
+  const int64_t* edge_key;
+};
+const int64_t* key_ptr(const c10::optional<at::Tensor>& x, const at::Tensor& ref, int64_t numel, const char* name) {
+  if (!x.has_value()) return nullptr;
+  dev_tensor(*x, at::kLong, name);
+  TORCH_CHECK(x->dim() == 1 && x->numel() == numel, name, " must be [", numel, "]");
+  same_device(ref, {&*x});
+  return x->data_ptr<int64_t>();
+}
+AttnDropArgs attn_drop_args(const at::Tensor& q, const at::Tensor& k, double p, int64_t seed, int64_t stream,
+                            const c10::optional<at::Tensor>& dst_key, const c10::optional<at::Tensor>& edge_key) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "p must be finite with 0 <= p < 1, got ", p);
+  TORCH_CHECK((float)p < 1.0f, "p rounds to 1 in float32");
+  TORCH_CHECK(seed >= 0, "seed must be a non-negative integer below 2^63");
+  TORCH_CHECK(stream >= 0, "stream must be non-negative");
+  return {(float)p, (uint64_t)seed, (uint64_t)stream, key_ptr(dst_key, q, q.size(0), "dst_key"),
+          key_ptr(edge_key, q, k.size(0), "edge_key")};
+}
+
+// drop null: tgnx_edge_attn_fwd / _bwd
+std::tuple<at::Tensor, at::Tensor> attn_fwd_impl(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                 const c10::optional<at::Tensor>& e, const at::Tensor& indptr,
+                                                 int64_t heads, const AttnDropArgs* drop) {
+  const c10::OptionalDeviceGuard guard(q.device());
+  const int64_t n = q.size(0), E = k.size(0), C = q.size(1) / heads;
+  at::Tensor out = at::empty_like(q), alpha = at::empty({E, heads}, q.options());
+  const float* ep = e.has_value() ? e->data_ptr<float>() : nullptr;
+  if (drop)
+    check_rc(tgnx_edge_attn_drop_fwd(n, E, (int32_t)heads, (int32_t)C, q.data_ptr<float>(), k.data_ptr<float>(),
+                                     v.data_ptr<float>(), ep, indptr.data_ptr<int64_t>(), out.data_ptr<float>(),
+                                     alpha.data_ptr<float>(), drop->p, drop->seed, drop->stream, drop->dst_key,
+                                     drop->edge_key, cur_stream()),
+             "tgnx_edge_attn_drop_fwd");
+  else
+    check_rc(tgnx_edge_attn_fwd(n, E, (int32_t)heads, (int32_t)C, q.data_ptr<float>(), k.data_ptr<float>(),
+                                v.data_ptr<float>(), ep, indptr.data_ptr<int64_t>(), out.data_ptr<float>(),
+                                alpha.data_ptr<float>(), cur_stream()),
+             "tgnx_edge_attn_fwd");
+  return {out, alpha};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> attn_bwd_impl(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const c10::optional<at::Tensor>& e, const at::Tensor& indptr, const at::Tensor& alpha, int64_t heads,
+    const AttnDropArgs* drop) {
+  const c10::OptionalDeviceGuard guard(q.device());
+  const int64_t n = q.size(0), E = k.size(0), C = q.size(1) / heads;
+  at::Tensor dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
+  at::Tensor de = e.has_value() ? at::empty_like(k) : at::empty({0}, k.options());
+  const float* ep = e.has_value() ? e->data_ptr<float>() : nullptr;
+  float* dep = e.has_value() ? de.data_ptr<float>() : nullptr;
+  if (drop)
+    check_rc(tgnx_edge_attn_drop_bwd(n, E, (int32_t)heads, (int32_t)C, dout.data_ptr<float>(), q.data_ptr<float>(),
+                                     k.data_ptr<float>(), v.data_ptr<float>(), ep, indptr.data_ptr<int64_t>(),
+                                     alpha.data_ptr<float>(), dq.data_ptr<float>(), dk.data_ptr<float>(),
+                                     dv.data_ptr<float>(), dep, drop->p, drop->seed, drop->stream, drop->dst_key,
+                                     drop->edge_key, cur_stream()),
+             "tgnx_edge_attn_drop_bwd");
+  else
+    check_rc(tgnx_edge_attn_bwd(n, E, (int32_t)heads, (int32_t)C, dout.data_ptr<float>(), q.data_ptr<float>(),
+                                k.data_ptr<float>(), v.data_ptr<float>(), ep, indptr.data_ptr<int64_t>(),
+                                alpha.data_ptr<float>(), dq.data_ptr<float>(), dk.data_ptr<float>(),
+                                dv.data_ptr<float>(), dep, cur_stream()),
+             "tgnx_edge_attn_bwd");
+  return {dq, dk, dv, de};
+}
+
+void attn_bwd_args(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& alpha,
+                   int64_t heads) {
+  dev_tensor(dout, at::kFloat, "dout");
+  dev_tensor(alpha, at::kFloat, "alpha");
+  TORCH_CHECK(dout.sizes() == q.sizes(), "dout must be [n_dst, H*C]");
+  TORCH_CHECK(alpha.dim() == 2 && alpha.size(0) == k.size(0) && alpha.size(1) == heads, "alpha must be [E, heads]");
+  same_device(q, {&dout, &alpha});
+}
+
 std::tuple<at::Tensor, at::Tensor> edge_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                                  const c10::optional<at::Tensor>& e, const at::Tensor& indptr,
                                                  int64_t heads) {
   attn_args(q, k, v, e, indptr, heads);
-  const c10::OptionalDeviceGuard guard(q.device());
-  const int64_t n = q.size(0), E = k.size(0), C = q.size(1) / heads;
-  at::Tensor out = at::empty_like(q), alpha = at::empty({E, heads}, q.options());
-  check_rc(tgnx_edge_attn_fwd(n, E, (int32_t)heads, (int32_t)C, q.data_ptr<float>(), k.data_ptr<float>(),
-                              v.data_ptr<float>(), e.has_value() ? e->data_ptr<float>() : nullptr,
-                              indptr.data_ptr<int64_t>(), out.data_ptr<float>(), alpha.data_ptr<float>(), cur_stream()),
-           "tgnx_edge_attn_fwd");
-  return {out, alpha};
+  return attn_fwd_impl(q, k, v, e, indptr, heads, nullptr);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_attn_bwd(
     const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     const c10::optional<at::Tensor>& e, const at::Tensor& indptr, const at::Tensor& alpha, int64_t heads) {
   attn_args(q, k, v, e, indptr, heads);
-  dev_tensor(dout, at::kFloat, "dout");
-  dev_tensor(alpha, at::kFloat, "alpha");
-  TORCH_CHECK(dout.sizes() == q.sizes(), "dout must be [n_dst, H*C]");
-  TORCH_CHECK(alpha.dim() == 2 && alpha.size(0) == k.size(0) && alpha.size(1) == heads, "alpha must be [E, heads]");
-  same_device(q, {&dout, &alpha});
-  const c10::OptionalDeviceGuard guard(q.device());
-  const int64_t n = q.size(0), E = k.size(0), C = q.size(1) / heads;
-  at::Tensor dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
-  at::Tensor de = e.has_value() ? at::empty_like(k) : at::empty({0}, k.options());
-  check_rc(tgnx_edge_attn_bwd(n, E, (int32_t)heads, (int32_t)C, dout.data_ptr<float>(), q.data_ptr<float>(),
-                              k.data_ptr<float>(), v.data_ptr<float>(), e.has_value() ? e->data_ptr<float>() : nullptr,
-                              indptr.data_ptr<int64_t>(), alpha.data_ptr<float>(), dq.data_ptr<float>(),
-                              dk.data_ptr<float>(), dv.data_ptr<float>(), e.has_value() ? de.data_ptr<float>() : nullptr,
-                              cur_stream()),
-           "tgnx_edge_attn_bwd");
-  return {dq, dk, dv, de};
+  attn_bwd_args(dout, q, k, alpha, heads);
+  return attn_bwd_impl(dout, q, k, v, e, indptr, alpha, heads, nullptr);
+}
+
+std::tuple<at::Tensor, at::Tensor> edge_attn_drop_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                      const c10::optional<at::Tensor>& e, const at::Tensor& indptr,
+                                                      int64_t heads, double p, int64_t seed, int64_t stream,
+                                                      const c10::optional<at::Tensor>& dst_key,
+                                                      const c10::optional<at::Tensor>& edge_key) {
+  attn_args(q, k, v, e, indptr, heads);
+  const AttnDropArgs d = attn_drop_args(q, k, p, seed, stream, dst_key, edge_key);
+  return attn_fwd_impl(q, k, v, e, indptr, heads, &d);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_attn_drop_bwd(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const c10::optional<at::Tensor>& e, const at::Tensor& indptr, const at::Tensor& alpha, int64_t heads, double p,
+    int64_t seed, int64_t stream, const c10::optional<at::Tensor>& dst_key,
+    const c10::optional<at::Tensor>& edge_key) {
+  attn_args(q, k, v, e, indptr, heads);
+  attn_bwd_args(dout, q, k, alpha, heads);
+  const AttnDropArgs d = attn_drop_args(q, k, p, seed, stream, dst_key, edge_key);
+  return attn_bwd_impl(dout, q, k, v, e, indptr, alpha, heads, &d);
 }
 
 // ------------------------------------------------------------------ backward ops (csrc/tgnx_ops_bwd.hip)
@@ -1290,6 +1372,13 @@ TORCH_LIBRARY(tgnx, m) {
   m.def("edge_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor? e, Tensor indptr, Tensor alpha, int heads) "
         "-> (Tensor, Tensor, Tensor, Tensor)",
         &edge_attn_bwd);
+  m.def("edge_attn_drop_fwd(Tensor q, Tensor k, Tensor v, Tensor? e, Tensor indptr, int heads, float p, int seed, "
+        "int stream, Tensor? dst_key, Tensor? edge_key) -> (Tensor, Tensor)",
+        &edge_attn_drop_fwd);
+  m.def("edge_attn_drop_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor? e, Tensor indptr, Tensor alpha, "
+        "int heads, float p, int seed, int stream, Tensor? dst_key, Tensor? edge_key) "
+        "-> (Tensor, Tensor, Tensor, Tensor)",
+        &edge_attn_drop_bwd);
   // backward ops (tgnx/ops.py wraps them as autograd functions); need[i] = 0 skips gradient i (returned empty)
   m.def("col_sum(Tensor x) -> Tensor", &col_sum);
   m.def("gru_update_bwd(Tensor dh_out, Tensor x, Tensor h, Tensor w_ih, Tensor w_hh, Tensor? b_ih, Tensor? b_hh, "

@@ -135,6 +135,11 @@ SIGNATURES = {
                                       c_vp]),
     "tgnx_edge_attn_fwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, c_vp]),
     "tgnx_edge_attn_bwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, P, P, P, P, c_vp]),
+    # ... p, seed, stream_id, dst_key, edge_key, stream
+    "tgnx_edge_attn_drop_fwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, ctypes.c_float,
+                                               c_u64, c_u64, P, P, c_vp]),
+    "tgnx_edge_attn_drop_bwd": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, P, P, P, P, P, P, P, P, P, P,
+                                               ctypes.c_float, c_u64, c_u64, P, P, c_vp]),
     # per-operator backward (tgnx_ops_bwd.hip)
     "tgnx_col_sum_ws_bytes": (c_sz, [c_i64, c_i64]),
     "tgnx_col_sum": (ctypes.c_int, [c_i64, c_i64, P, c_i64, P, P, c_sz, c_vp]),

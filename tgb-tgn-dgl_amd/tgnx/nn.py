@@ -103,8 +103,16 @@ class MemoryCell(nn.Module):
 class TransformerConv(nn.Module):
     """torch_geometric.nn.TransformerConv(in, out, heads, dropout=, edge_dim=) with concat=True, beta=False,
     root_weight=True: out_i = Σ_j α_ij (W_v x_j + W_e e_ij) + W_skip x_i, α the per-destination softmax of
-    (W_q x_i)·(W_k x_j + W_e e_ij) / sqrt(out).  The attention ops apply no dropout: training mode with
-    dropout > 0 raises NotImplementedError; eval() or dropout=0.0 runs."""
+    (W_q x_i)·(W_k x_j + W_e e_ij) / sqrt(out).
+
+    Attention dropout (training mode, dropout > 0) is applied to α after the softmax under the engine's counter-based
+    mask (ops.edge_attention), a function of a seed and not of torch's RNG.  The module must therefore know a seed:
+    pass forward(..., seed=) per call, or call set_dropout_seed(base) once, after which the nb-th training forward
+    uses ops.step_seed(base, nb) as the engine's nb-th batch does.  Without either, a training forward at
+    dropout > 0 raises NotImplementedError; eval() or dropout=0.0 runs without a seed.  The mask's keys default to
+    the row of x for a destination and the edge's column in the caller's edge_index for an edge (so an edge's mask
+    does not depend on how the list was ordered); dst_key [N] / edge_key [E] (int64, e.g. node ids and event ids)
+    replace them."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, dropout: float = 0.0,
                  edge_dim: int | None = None):
@@ -118,16 +126,36 @@ class TransformerConv(nn.Module):
         self.lin_value = nn.Linear(in_channels, heads * out_channels)
         self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
         self.lin_skip = nn.Linear(in_channels, heads * out_channels)
+        # plain attributes (not buffers: state_dict() keeps the reference's keys)
+        self._drop_base, self._drop_calls = None, 0
 
     def reset_parameters(self):
         for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_edge, self.lin_skip):
             lin.reset_parameters()
 
-    def forward(self, x, edge_index, edge_attr):
-        if self.training and self.dropout > 0:
-            raise NotImplementedError(
-                "tgnx.nn.TransformerConv: attention dropout is not implemented by the attention ops; call eval() "
-                "or construct with dropout=0.0 to train without it")
+    def set_dropout_seed(self, base_seed: int | None):
+        """Enable attention dropout in training forwards that pass no seed: the nb-th such forward from now on
+        (nb = 1, 2, ...) uses ops.step_seed(base_seed, nb).  None switches back to raising."""
+        self._drop_base = None if base_seed is None else int(base_seed)
+        self._drop_calls = 0
+
+    def take_dropout_seed(self):
+        """What a training forward without an explicit seed does first, in host arithmetic only: advance the call
+        counter and return ops.step_seed(base, counter); None (and no advance) when no base seed is set."""
+        if self._drop_base is None:
+            return None
+        self._drop_calls += 1
+        return ops.step_seed(self._drop_base, self._drop_calls)
+
+    def forward(self, x, edge_index, edge_attr, *, seed=None, dst_key=None, edge_key=None):
+        drop = self.training and self.dropout > 0
+        if drop and seed is None:
+            seed = self.take_dropout_seed()
+            if seed is None:
+                raise NotImplementedError(
+                    "tgnx.nn.TransformerConv: attention dropout in training mode needs a seed (the mask is a "
+                    "counter-based hash, not torch's RNG): pass forward(..., seed=) or call set_dropout_seed(base) "
+                    "once; or call eval() / construct with dropout=0.0 to run without dropout")
         n = x.size(0)
         src, dst = edge_index[0], edge_index[1]                     # flow source_to_target
         q = ops.linear(x, self.lin_query.weight, self.lin_query.bias)
@@ -139,13 +167,18 @@ class TransformerConv(nn.Module):
         indptr = torch.zeros(n + 1, dtype=torch.long, device=x.device)
         indptr[1:] = torch.cumsum(torch.bincount(dst_sorted, minlength=n), 0)
         j = src[perm]
-        out, _ = ops.edge_attention(q, k[j], v[j], e[perm], indptr, self.heads)
+        if drop:  # an edge's key: the caller's, or its column in the caller's edge_index (not its sorted position)
+            out, _ = ops.edge_attention(q, k[j], v[j], e[perm], indptr, self.heads, dropout=self.dropout, seed=seed,
+                                        dst_key=dst_key, edge_key=perm if edge_key is None else edge_key[perm])
+        else:
+            out, _ = ops.edge_attention(q, k[j], v[j], e[perm], indptr, self.heads)
         return out + ops.linear(x, self.lin_skip.weight, self.lin_skip.bias)
 
 
 class GraphAttentionEmbedding(nn.Module):
     """modules/emb_module.py:11-29: one TransformerConv (2 heads of out_channels // 2) over edge attributes
-    [time_enc(last_update[src] - t), msg].  `dropout` is the reference's fixed 0.1 (see TransformerConv)."""
+    [time_enc(last_update[src] - t), msg].  `dropout` is the reference's fixed 0.1; training with it needs a
+    seed, per call or through set_dropout_seed (see TransformerConv), and seed / dst_key / edge_key pass through."""
 
     def __init__(self, in_channels: int, out_channels: int, msg_dim: int, time_enc: nn.Module, dropout: float = 0.1):
         super().__init__()
@@ -153,11 +186,14 @@ class GraphAttentionEmbedding(nn.Module):
         edge_dim = msg_dim + time_enc.out_channels
         self.conv = TransformerConv(in_channels, out_channels // 2, heads=2, dropout=dropout, edge_dim=edge_dim)
 
-    def forward(self, x, last_update, edge_index, t, msg):
+    def set_dropout_seed(self, base_seed: int | None):
+        self.conv.set_dropout_seed(base_seed)
+
+    def forward(self, x, last_update, edge_index, t, msg, *, seed=None, dst_key=None, edge_key=None):
         rel_t = last_update[edge_index[0]] - t
         rel_t_enc = self.time_enc(rel_t.to(x.dtype))
         edge_attr = torch.cat([rel_t_enc, msg], dim=-1)
-        return self.conv(x, edge_index, edge_attr)
+        return self.conv(x, edge_index, edge_attr, seed=seed, dst_key=dst_key, edge_key=edge_key)
 
 
 class _NormalLinear(nn.Linear):

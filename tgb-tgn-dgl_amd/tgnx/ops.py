@@ -13,7 +13,8 @@ in, csrc/tgnx_topk.hip; `link_topk` below; predictor_topk_filtered / predictor_t
 exclusions by key / a candidate list per source; predictor_loo: the logit of explicit pairs with one side's embedding
 replaced by each of its leave-one-out rows, csrc/tgnx_explain.hip; `link_loo` below), embed_knn (nearest neighbours in embedding space, dot or cosine, on the
 f32 MFMA with the same selection and exclusions, csrc/tgnx_knn.hip; `embed_knn` below) and edge_attn_fwd / edge_attn_bwd (TransformerConv's attention,
-emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function), time_encode (TimeEncoder)
+emb_module.py:21-29; `edge_attention` below wraps the pair as an autograd function; edge_attn_drop_fwd /
+edge_attn_drop_bwd: the same with attention dropout under the engine's counter-based mask), time_encode (TimeEncoder)
 and time_embedding (TimeEmbedding, emb_module.py:32-52).  The backward halves (csrc/tgnx_ops_bwd.hip: col_sum,
 gru_update_bwd, predictor_bwd, time_encode_bwd, time_embedding_bwd, msg_agg_last_bwd, msg_agg_mean_bwd) sit
 behind the autograd functions below — memory_cell, link_predictor, time_encode, time_embedding, aggregate_last,
@@ -34,6 +35,7 @@ import torch
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtgnx_torch.so")
 OPS = ("ring_reset", "ring_sample", "ring_insert", "neg_sample", "block_ids", "tcsr_build", "tcsr_sample", "gemm_f32",
        "msg_agg_last", "msg_agg_mean", "gru_update", "predictor", "predictor_topk", "edge_attn_fwd", "edge_attn_bwd",
+       "edge_attn_drop_fwd", "edge_attn_drop_bwd",
        "predictor_topk_filtered", "predictor_topk_lists", "predictor_rank", "predictor_loo", "embed_knn",
        "sample_recent", "insert_recent", "reset",
        "col_sum", "gru_update_bwd", "predictor_bwd", "time_encode", "time_encode_bwd", "time_embedding",
@@ -73,15 +75,77 @@ class _EdgeAttention(torch.autograd.Function):
         return dq, dk, dv, (de if ctx.has_e else None), None, None
 
 
-def edge_attention(q, k, v, e, indptr, heads):
+class _EdgeAttentionDrop(torch.autograd.Function):
+    """edge_attn_drop_fwd / _bwd: α (before dropout) and the keys are saved, the mask is not — the backward
+    recomputes it from (p, seed, stream, keys)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, e, indptr, heads, p, seed, stream, dst_key, edge_key):
+        out, alpha = load().edge_attn_drop_fwd(q, k, v, e, indptr, heads, p, seed, stream, dst_key, edge_key)
+        empty = indptr.new_empty(0)
+        ctx.save_for_backward(q, k, v, e if e is not None else q.new_empty(0), indptr, alpha,
+                              dst_key if dst_key is not None else empty, edge_key if edge_key is not None else empty)
+        ctx.heads, ctx.has_e, ctx.drop = heads, e is not None, (p, seed, stream)
+        ctx.has_keys = (dst_key is not None, edge_key is not None)
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, dout, _dalpha):
+        q, k, v, e, indptr, alpha, dst_key, edge_key = ctx.saved_tensors
+        p, seed, stream = ctx.drop
+        dq, dk, dv, de = load().edge_attn_drop_bwd(
+            dout.contiguous(), q, k, v, e if ctx.has_e else None, indptr, alpha, ctx.heads, p, seed, stream,
+            dst_key if ctx.has_keys[0] else None, edge_key if ctx.has_keys[1] else None)
+        return (dq, dk, dv, (de if ctx.has_e else None)) + (None,) * 7
+
+
+ATTN_DROPOUT_STREAM = 7  # the hash stream of the engine's conv attention dropout (9: conv2)
+
+
+def step_seed(base_seed: int, nb: int) -> int:
+    """The engine's per-batch dropout seed, mix64(base_seed ^ mix64(nb)) >> 1 (splitmix64's output function, nb =
+    the batch counter after its advance), in host integer arithmetic."""
+    m = (1 << 64) - 1
+
+    def mix64(z):
+        z = (z + 0x9E3779B97F4A7C15) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return z ^ (z >> 31)
+
+    return mix64((int(base_seed) & m) ^ mix64(int(nb) & m)) >> 1
+
+
+def edge_attention(q, k, v, e, indptr, heads, dropout=0.0, seed=None, stream=ATTN_DROPOUT_STREAM, dst_key=None,
+                   edge_key=None):
     """TransformerConv's attention (PyG semantics, emb_module.py:21-29) with autograd: q [n_dst, H*C] per
     destination; k, v, e [E, H*C] per edge, destination i's edges the rows [indptr[i], indptr[i+1]) (e may be
     None).  Returns (out [n_dst, H*C], alpha [E, H]); gradients flow to q, k, v, e.  1 <= heads <= 8 and
     H*C <= 256 (RuntimeError otherwise).  indptr (non-decreasing) need not span all E rows: an edge row that no
     destination owns, before indptr[0] or from indptr[-1] on, and every row when n_dst == 0, has alpha = 0 and
-    receives zero gradients in k, v and e."""
-    return _EdgeAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(),
-                                None if e is None else e.contiguous(), indptr, int(heads))
+    receives zero gradients in k, v and e.
+
+    dropout > 0 applies attention dropout after the softmax (PyG's order): out_i = Σ_p (α_p m_p)(v_p + e_p) with the
+    counter-based mask m[p, h] = keep32(drop_base(seed, stream, dst_key[i], edge_key[p]), h) of csrc/tgnx_math.h
+    (tests/dropout_ref.py restates it), 0 or 1 / (1 - dropout); alpha stays the softmax before dropout.  seed (an int in
+    [0, 2^63)) is required then (ValueError without); dst_key [n_dst] / edge_key [E] are optional int64 tensors
+    (default: the row numbers).  With stream 7, the centres' node ids, the edges' event ids and a batch's step seed
+    the mask is the fused train step's.  dropout == 0 is exactly the call without these arguments."""
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    e = None if e is None else e.contiguous()
+    if dropout == 0:
+        return _EdgeAttention.apply(q, k, v, e, indptr, int(heads))
+    if seed is None:
+        raise ValueError("edge_attention: dropout > 0 needs a seed (the mask is a function of it, not of torch's RNG)")
+    seed = int(seed)
+    if not 0 <= seed < (1 << 63):
+        raise ValueError("edge_attention: seed must be a non-negative integer below 2^63")
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("edge_attention: dropout must be in [0, 1)")
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    return _EdgeAttentionDrop.apply(q, k, v, e, indptr, int(heads), float(dropout), seed, int(stream), c(dst_key),
+                                    c(edge_key))
 
 
 def _grads(outs, need):
